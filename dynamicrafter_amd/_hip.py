@@ -44,6 +44,18 @@ class DcDdimParams(C.Structure):
     ]
 
 
+class DcDpmParams(C.Structure):
+    _fields_ = [
+        ("A", C.c_void_p), ("alpha_t", C.c_void_p), ("alpha_p_r", C.c_void_p), ("k", C.c_void_p), ("N", C.c_void_p),
+        ("sqrt_one_minus_at", C.c_void_p), ("sqrt_acp_t", C.c_void_p), ("sqrt_1macp_t", C.c_void_p),
+        ("scale_ratio", C.c_void_p), ("step_index", C.c_void_p),
+        ("index", C.c_int), ("v_param", C.c_int),
+        ("cfg_scale", C.c_float), ("cfg_img", C.c_float), ("guidance_rescale", C.c_float),
+        ("temperature", C.c_float),
+        ("e_nchw", C.c_int), ("noise_step_stride", C.c_int64), ("x0_hist", C.c_void_p),
+    ]
+
+
 # name -> (restype, argtypes); must list every symbol include/dcrafter_hip.h declares
 _P, _I, _F, _L = C.c_void_p, C.c_int, C.c_float, C.c_int64
 SIGNATURES = {
@@ -80,6 +92,7 @@ SIGNATURES = {
     "dc_add_rows": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _P]),
     "dc_vae_sample": (_I, [_P, _I, _P, _P, _I, _I, _I, _F, _P]),
     "dc_ddim_step": (_I, [C.POINTER(DcDdimParams), _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    "dc_dpmpp_step": (_I, [C.POINTER(DcDpmParams), _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
     "dc_attn_small": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _P]),
     "dc_attn_small_lds_bytes": (_L, [_I, _I]),
     "dc_clip_preprocess": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), _P]),

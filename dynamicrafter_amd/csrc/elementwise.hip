@@ -354,6 +354,65 @@ __global__ __launch_bounds__(256) void ddim_apply_kernel(const DcDdimParams p, c
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// DPM-Solver++ 2M / 2M SDE update (data-prediction multistep form). The guidance-rescale statistics come from
+// ddim_partial_kernel (same workspace layout, same fixed reduction order), launched with a DcDdimParams `q` that
+// carries the CFG fields; this one pass converts the model output to the raw x0_i, forms
+// D = (1 + k) x0_i - k x0_{i-1} with x0_{i-1} from the history ring, and writes x_prev, pred_x0 = r x0_i and x0_i.
+// Per element: e_c, e_u [, e_i], x, x0_{i-1}, noise in; x_prev, pred_x0, x0_i out.
+__global__ __launch_bounds__(256) void dpmpp_apply_kernel(const DcDpmParams p, const DcDdimParams q,
+                                                          const float* __restrict__ ec, const float* __restrict__ eu,
+                                                          const float* __restrict__ ei, int ld_e,
+                                                          const float* x,      // x and x_prev may alias (in place)
+                                                          const float* __restrict__ noise, float* x_prev,
+                                                          float* __restrict__ pred_x0, int C, int THW, int64_t n_all,
+                                                          const float* __restrict__ ws) {
+    __shared__ double tot[4];
+    const int b = blockIdx.y;
+    const int64_t n = (int64_t)C * THW;
+    float factor = 1.0f;   // guidance rescale, as ddim_apply_kernel
+    if (p.guidance_rescale > 0.f && eu) {
+        if (threadIdx.x < 4) {
+            double t = 0.0;
+            for (int k = 0; k < DDIM_BLOCKS; ++k) t += (double)ws[((size_t)b * DDIM_BLOCKS + k) * 4 + threadIdx.x];
+            tot[threadIdx.x] = t;
+        }
+        __syncthreads();
+        const double cnt = (double)n;
+        const double mean_cfg = tot[0] / cnt, mean_txt = tot[2] / cnt;
+        const double var_cfg = fmax(tot[1] - cnt * mean_cfg * mean_cfg, 0.0) / (cnt - 1.0);
+        const double var_txt = fmax(tot[3] - cnt * mean_txt * mean_txt, 0.0) / (cnt - 1.0);
+        const float ratio = (float)sqrt(var_txt) / (float)sqrt(var_cfg);
+        factor = p.guidance_rescale * ratio + (1.f - p.guidance_rescale);
+    }
+    const int idx = p.step_index ? p.step_index[0] : p.index;
+    if (noise && p.step_index) noise += (size_t)idx * p.noise_step_stride;
+    const float A = p.A[idx], al_t = p.alpha_t[idx], al_pr = p.alpha_p_r[idx], kk = p.k[idx];
+    const float ncoef = p.N ? p.N[idx] * p.temperature : 0.f;
+    const float s1m = p.v_param ? 0.f : p.sqrt_one_minus_at[idx];
+    const float sq_acp = p.v_param ? p.sqrt_acp_t[idx] : 0.f;
+    const float sq_1macp = p.v_param ? p.sqrt_1macp_t[idx] : 0.f;
+    const float resc = p.scale_ratio ? p.scale_ratio[idx] : 1.0f;
+    float* __restrict__ cur = p.x0_hist + (size_t)(idx & 1) * n_all;
+    const float* __restrict__ prev = p.x0_hist + (size_t)((idx + 1) & 1) * n_all;
+    const bool second = kk != 0.f;   // uniform over the grid: a first-order step never reads the (maybe stale) slot
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int c = (int)(i / THW), pos = (int)(i - (int64_t)c * THW);     // NCTHW order for x / outputs
+        const size_t eoff = ddim_eoff(q, b, c, pos, C, THW, ld_e);
+        const size_t xoff = (size_t)b * n + i;
+        const float mo = ddim_cfg(q, ec, eu, ei, eoff) * factor;
+        const float xv = x[xoff];
+        // raw data prediction: predict_start_from_z_and_v ddpm3d.py:239-245 / ddim.py:258
+        const float x0 = p.v_param ? sq_acp * xv - sq_1macp * mo : (xv - s1m * mo) / al_t;
+        const float d = second ? (1.f + kk) * x0 - kk * prev[xoff] : x0;
+        float xp = A * (xv - al_t * d) + al_pr * d;
+        if (noise) xp += ncoef * noise[xoff];
+        x_prev[xoff] = xp;
+        pred_x0[xoff] = resc * x0;
+        cur[xoff] = x0;
+    }
+}
+
 
 // dst[c][r] = src[r][c] for bf16 rows; 64x64 tiles through LDS (pad column against bank conflicts)
 __global__ __launch_bounds__(256) void transpose_kernel(const bf16_t* __restrict__ src, int lds_, bf16_t* __restrict__ dst,
@@ -553,6 +612,36 @@ extern "C" int dc_ddim_step(const DcDdimParams* pp, const float* e_cond, const f
     const int64_t n = (int64_t)C * THW;
     hipLaunchKernelGGL(ddim_apply_kernel, dim3(grid_for(n, 256, 1024), B), dim3(256), 0, stream, p, e_cond, e_uncond,
                        e_img, ld_e, x, noise, x_prev, pred_x0, C, THW, workspace);
+    DC_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dc_dpmpp_step(const DcDpmParams* pp, const float* e_cond, const float* e_uncond, const float* e_img,
+                             int ld_e, const float* x, const float* noise, float* x_prev, float* pred_x0, int B, int C,
+                             int THW, float* workspace, void* stream_) {
+    if (!pp || !e_cond || !x || !x_prev || !pred_x0 || !workspace) return DC_ERR_ARG;
+    const DcDpmParams& p = *pp;
+    if (!p.A || !p.alpha_t || !p.alpha_p_r || !p.k || !p.x0_hist) return DC_ERR_ARG;
+    if (p.v_param ? (!p.sqrt_acp_t || !p.sqrt_1macp_t) : !p.sqrt_one_minus_at) return DC_ERR_ARG;
+    if (p.N && !noise) return DC_ERR_ARG;                 // the SDE variant needs its per-step draw
+    if (e_img && !e_uncond) return DC_ERR_ARG;
+    if (B < 1 || C < 1 || THW < 1) return DC_ERR_SHAPE;
+    if (!p.e_nchw && ld_e < C) return DC_ERR_SHAPE;
+    // the CFG fields in the layout ddim_partial_kernel / ddim_cfg / ddim_eoff read
+    DcDdimParams q = {};
+    q.cfg_scale = p.cfg_scale;
+    q.cfg_img = p.cfg_img;
+    q.guidance_rescale = p.guidance_rescale;
+    q.e_nchw = p.e_nchw;
+    hipStream_t stream = (hipStream_t)stream_;
+    if (p.guidance_rescale > 0.f && e_uncond) {
+        hipLaunchKernelGGL(ddim_partial_kernel, dim3(DDIM_BLOCKS, B), dim3(256), 0, stream, q, e_cond, e_uncond, e_img,
+                           ld_e, C, THW, workspace);
+        DC_CHECK_LAUNCH();
+    }
+    const int64_t n = (int64_t)C * THW;
+    hipLaunchKernelGGL(dpmpp_apply_kernel, dim3(grid_for(n, 256, 1024), B), dim3(256), 0, stream, p, q, e_cond, e_uncond,
+                       e_img, ld_e, x, noise, x_prev, pred_x0, C, THW, n * B, workspace);
     DC_CHECK_LAUNCH();
     return 0;
 }

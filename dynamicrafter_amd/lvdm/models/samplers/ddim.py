@@ -72,9 +72,13 @@ class FusedRun:
         M = self.kw["B"] * self.kw["THW"]
         e_u = e[M:2 * M] if self.nb > 1 else None
         e_i = e[2 * M:3 * M] if self.nb > 2 else None
-        ops.ddim_step(self.sampler._tables, e[:M], e_u, e_i, self.img, self.noises, self.img, self.pred_x0, self.ws,
-                      step_index=self.counter, **self.kw)
+        self._update(e[:M], e_u, e_i)
         ops.advance_counter(self.counter)
+
+    def _update(self, e_c, e_u, e_i):
+        """The sampler's update kernel of one step (the fused DDIM step here; samplers/dpm_solver.py overrides it)."""
+        ops.ddim_step(self.sampler._tables, e_c, e_u, e_i, self.img, self.noises, self.img, self.pred_x0, self.ws,
+                      step_index=self.counter, **self.kw)
 
     def capture(self):
         """Warm up once eagerly (allocates all scratch), restore the state, capture one step into a hipGraph."""

@@ -715,6 +715,40 @@ def ddim_step(tables, e_cond, e_uncond, e_img, x, noise, x_prev, pred_x0, worksp
     return x_prev, pred_x0
 
 
+def dpmpp_step(tables, e_cond, e_uncond, e_img, x, noise, x_prev, pred_x0, workspace, x0_hist, *, B, Cc, THW, index=0,
+               step_index=None, v_param=False, cfg_scale=1.0, cfg_img=1.0, guidance_rescale=0.0, temperature=1.0,
+               e_nchw=False, ld_e=None, noise_step_stride=0):
+    """One DPM-Solver++ (2M / 2M SDE) update (dc_dpmpp_step). tables: dict of fp32 device vectors in execution order -
+    the solver's dpm_A, dpm_alpha_t, dpm_alpha_p_r, dpm_k [, dpm_N] and the DDIM sampler's sqrt_one_minus_at /
+    sqrt_acp_t / sqrt_1macp_t [/ scale_ratio]. x0_hist: [2, B*C*THW] fp32 ring of raw data predictions."""
+    n = B * Cc * THW
+    for t, nm in ((x, "x"), (x_prev, "x_prev"), (pred_x0, "pred_x0")):
+        _need(t, n, nm)
+    _need(x0_hist, 2 * n, "x0_hist")
+    _need(workspace, 16 * B * 256, "workspace")
+    if tables.get("dpm_N") is not None:
+        steps = int(tables["dpm_N"].numel()) if step_index is not None else 1
+        _need(noise, (steps - 1) * noise_step_stride + n if step_index is not None else n, "noise")
+    p = _hip.DcDpmParams()
+    for k in ("A", "alpha_t", "alpha_p_r", "k", "N"):
+        t = tables.get("dpm_" + k)
+        setattr(p, k, 0 if t is None else t.data_ptr())
+    for k in ("sqrt_one_minus_at", "sqrt_acp_t", "sqrt_1macp_t", "scale_ratio"):
+        t = tables.get(k)
+        setattr(p, k, 0 if t is None else t.data_ptr())
+    p.step_index = 0 if step_index is None else step_index.data_ptr()
+    p.index, p.v_param = index, 1 if v_param else 0
+    p.cfg_scale, p.cfg_img, p.guidance_rescale, p.temperature = cfg_scale, cfg_img, guidance_rescale, temperature
+    p.e_nchw, p.noise_step_stride = 1 if e_nchw else 0, noise_step_stride
+    p.x0_hist = x0_hist.data_ptr()
+    if ld_e is None:
+        ld_e = 0 if e_nchw else e_cond.stride(0)
+    check(_hip.lib().dc_dpmpp_step(C.byref(p), _ptr(e_cond), _ptr(e_uncond), _ptr(e_img), ld_e, _ptr(x), _ptr(noise),
+                                   _ptr(x_prev), _ptr(pred_x0), B, Cc, THW, _ptr(workspace), stream_ptr()),
+          "dc_dpmpp_step")
+    return x_prev, pred_x0
+
+
 def mask_blend(img, x0, mask, qnoise, tables, *, index=0, step_index=None, clean=False, noise_step_stride=0):
     """img = orig*mask + (1-mask)*img in place, orig = x0 or its q_sample at the step's timestep (fp32, same shapes)."""
     n = img.numel()

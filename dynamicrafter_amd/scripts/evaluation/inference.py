@@ -1,7 +1,7 @@
 """Host harness of the hot path: the counterpart of the reference's `scripts/evaluation/inference.py` functions that
 sit between the data loader and the sampler.
 
-    image_guided_synthesis   inference.py:216-313   conditioning assembly -> DDIM loop -> first-stage decode
+    image_guided_synthesis   inference.py:216-313   conditioning assembly -> DDIM (or DPM-Solver++) loop -> decode
     get_latent_z             inference.py:164-169   video -> per-frame AE latents
     load_model_checkpoint    inference.py:34-59     Lightning / DeepSpeed state dict -> model (key renames kept)
 
@@ -16,6 +16,8 @@ import torch
 
 from ...lvdm.models.samplers.ddim import DDIMSampler
 from ...lvdm.models.samplers.ddim_multiplecond import DDIMSampler as DDIMSampler_multicond
+from ...lvdm.models.samplers.dpm_solver import SOLVERS as DPM_SOLVERS
+from ...lvdm.models.samplers.dpm_solver import DPMSolverSampler
 
 
 def load_model_checkpoint(model, ckpt):
@@ -55,15 +57,23 @@ def get_latent_z(model, videos):
 def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddim_steps=50, ddim_eta=1.,
                            unconditional_guidance_scale=1.0, cfg_img=None, fs=None, text_input=False,
                            multiple_cond_cfg=False, loop=False, interp=False, timestep_spacing="uniform",
-                           guidance_rescale=0.0, use_fixed_scheduler=False, **kwargs):
+                           guidance_rescale=0.0, use_fixed_scheduler=False, sampler="ddim", **kwargs):
     """inference.py:216-313. Returns [batch, n_samples, c, t, h, w] decoded frames.
 
     `use_fixed_scheduler` is accepted and ignored: the fork's "fixed" sampler only patches sigma so that
     1 - a_prev - sigma^2 cannot go negative (inference.py:172-214); the step kernel here clamps that radicand at zero
     (csrc/elementwise.hip), which is the same guard at the point of use.
     Extra keyword arguments (e.g. `x_T`, `noises`, `use_graph`) are passed to `DDIMSampler.sample` as the reference
-    passes its **kwargs."""
-    ddim_sampler = DDIMSampler_multicond(model) if multiple_cond_cfg else DDIMSampler(model)
+    passes its **kwargs.
+    `sampler` (not in the reference): "ddim" (default, the reference's sampler), or "dpmpp_2m" / "dpmpp_2m_sde" for
+    DPM-Solver++ on the same timesteps (lvdm/models/samplers/dpm_solver.py; `ddim_steps` is then its step count and
+    `ddim_eta` is not used)."""
+    if sampler == "ddim":
+        ddim_sampler = DDIMSampler_multicond(model) if multiple_cond_cfg else DDIMSampler(model)
+    elif sampler in DPM_SOLVERS:
+        ddim_sampler = DPMSolverSampler(model, solver=sampler)
+    else:
+        raise ValueError(f"sampler must be 'ddim' or one of {DPM_SOLVERS}, got {sampler!r}")
     ddim_sampler.make_schedule(ddim_num_steps=ddim_steps, ddim_discretize=timestep_spacing, ddim_eta=ddim_eta, verbose=False)
 
     batch_size = noise_shape[0]

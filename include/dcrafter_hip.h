@@ -206,6 +206,44 @@ int dc_ddim_step(const DcDdimParams* p, const float* e_cond, const float* e_unco
                  const float* x, const float* noise, float* x_prev, float* pred_x0, int B, int C, int THW,
                  float* workspace, void* stream);
 
+typedef struct DcDpmParams {
+    /* per-step fp32 tables in execution order, indexed by step_index[0] (device) when step_index != NULL, else by
+     * `index`. The solver's own tables (host float64 -> fp32, samplers/dpm_solver.py): */
+    const float* A;              /* sigma_p/sigma_t (2M) or (sigma_p/sigma_t) e^-h (2M SDE) */
+    const float* alpha_t;        /* sqrt(ddim_alphas[index]) */
+    const float* alpha_p_r;      /* sqrt(ddim_alphas_prev[index]) * r, r = scale_arr_prev/scale_arr or 1 */
+    const float* k;              /* second-order weight 1/(2 rho); 0 -> first order (the previous x0 is not read) */
+    const float* N;              /* noise coefficient sigma_p sqrt(1 - e^-2h) (2M SDE) or NULL (2M) */
+    /* the DDIM sampler's tables, for the model-output conversion (same fp32 values dc_ddim_step reads): */
+    const float* sqrt_one_minus_at;  /* sigma_t (eps-param) */
+    const float* sqrt_acp_t;         /* model.sqrt_alphas_cumprod[t]           (v-param) */
+    const float* sqrt_1macp_t;       /* model.sqrt_one_minus_alphas_cumprod[t] (v-param) */
+    const float* scale_ratio;        /* r for pred_x0 = r x0_i, or NULL (r = 1) */
+    const int32_t* step_index;   /* device counter or NULL */
+    int index;
+    int v_param;
+    float cfg_scale;
+    float cfg_img;
+    float guidance_rescale;
+    float temperature;
+    int e_nchw;                  /* as DcDdimParams */
+    int64_t noise_step_stride;   /* with step_index: noise for this step starts at noise + step_index[0]*stride */
+    float* x0_hist;              /* ring [2][B*C*THW] fp32 of raw data predictions: step i reads slot (i-1)&1, writes slot i&1 */
+} DcDpmParams;
+
+/* One DPM-Solver++ (2M / 2M SDE) multistep update for B clips, in the data-prediction form
+ *   x0_i  = raw data prediction (after CFG and guidance rescale, before dynamic rescale)
+ *   D     = (1 + k) x0_i - k x0_{i-1}
+ *   x_prev = A (x - alpha_t D) + alpha_p_r D + N temperature noise
+ * which is dc_ddim_step's eta = 0 update when k = 0 and A = sigma_p/sigma_t. Operands as in dc_ddim_step (x and x_prev
+ * may alias); pred_x0 receives r x0_i (dc_ddim_step's pred_x0); noise may be NULL when p->N is NULL.
+ * workspace: >= 16 * B * 256 floats.
+ * replaces (generalises): p_sample_ddim lvdm/models/samplers/ddim.py:226-277 + rescale_noise_cfg
+ * utils_diffusion.py:147-157 (multistep solver: Lu et al., DPM-Solver++, arXiv:2211.01095, Alg. 2) */
+int dc_dpmpp_step(const DcDpmParams* p, const float* e_cond, const float* e_uncond, const float* e_img, int ld_e,
+                  const float* x, const float* noise, float* x_prev, float* pred_x0, int B, int C, int THW,
+                  float* workspace, void* stream);
+
 /* DynamiCrafter's dual cross-attention in one launch: o = softmax(s q k^T) v + scale2 * softmax(s q k2^T) v2 with two
  * independent softmaxes (text keys Lk, image keys Lk2) over the same queries; head_dim 64. q/o rows as in
  * dc_flash_attn_d64; k, v, k2, v2 rows share the stride ldkv and the batch stride kv_bstride (views into one fused
