@@ -56,6 +56,16 @@ class DcDpmParams(C.Structure):
     ]
 
 
+class DcSdsParams(C.Structure):
+    _fields_ = [
+        ("c1", C.c_void_p), ("c2", C.c_void_p), ("w", C.c_void_p), ("step_size", C.c_void_p), ("bc2_sqrt", C.c_void_p),
+        ("step_index", C.c_void_p), ("index", C.c_int), ("weight_type", C.c_int), ("x0_param", C.c_int),
+        ("e_nchw", C.c_int), ("cfg_scale", C.c_float), ("guidance_rescale", C.c_float),
+        ("beta2", C.c_float), ("eps", C.c_float), ("one_minus_beta1", C.c_float), ("one_minus_beta2", C.c_float),
+        ("decay", C.c_float), ("grad_scale", C.c_float), ("noise_step_stride", C.c_int64), ("loss", C.c_void_p),
+    ]
+
+
 # name -> (restype, argtypes); must list every symbol include/dcrafter_hip.h declares
 _P, _I, _F, _L = C.c_void_p, C.c_int, C.c_float, C.c_int64
 SIGNATURES = {
@@ -93,6 +103,8 @@ SIGNATURES = {
     "dc_vae_sample": (_I, [_P, _I, _P, _P, _I, _I, _I, _F, _P]),
     "dc_ddim_step": (_I, [C.POINTER(DcDdimParams), _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
     "dc_dpmpp_step": (_I, [C.POINTER(DcDpmParams), _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    "dc_sds_noise": (_I, [C.POINTER(DcSdsParams), _P, _P, _P, _I, _L, _P]),
+    "dc_sds_step": (_I, [C.POINTER(DcSdsParams), _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
     "dc_attn_small": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _I, _F, _I, _P]),
     "dc_attn_small_lds_bytes": (_L, [_I, _I]),
     "dc_clip_preprocess": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, C.POINTER(_F), C.POINTER(_F), _P]),

@@ -413,6 +413,163 @@ __global__ __launch_bounds__(256) void dpmpp_apply_kernel(const DcDpmParams p, c
     }
 }
 
+// ---------------------------------------------------------------------------------------------------------
+// Score distillation (SDS) with an Adam / AdamW step on the latent. The noising pass writes x_t = c1 L + c2 eps[k].
+// The update reuses ddim_partial_kernel for the guidance-rescale statistics (launched with a DcDdimParams `q` that
+// carries the CFG fields); "ada" adds one per-clip reduction of |d|; sds_apply_kernel forms the gradient, updates
+// m, v and L in place and leaves per-block partial sums of grad^2, which sds_loss_kernel reduces in a fixed order.
+// Every step of torch's arithmetic is rounded separately, as torch evaluates it: no FMA contraction here.
+constexpr int SDS_APPLY_BLOCKS = 1024;   // cap on apply-pass blocks per clip (= loss partials per clip)
+
+__global__ __launch_bounds__(256) void sds_noise_kernel(const DcSdsParams p, const float* __restrict__ L,
+                                                        const float* __restrict__ noise, float* __restrict__ xt,
+                                                        int64_t n) {
+#pragma clang fp contract(off)
+    const int b = blockIdx.y, B = gridDim.y;
+    const int k = p.step_index ? p.step_index[0] : p.index;
+    if (p.step_index) noise += (size_t)k * p.noise_step_stride;
+    const float a = p.c1[(size_t)k * B + b], s = p.c2[(size_t)k * B + b];
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const size_t off = (size_t)b * n + i;
+        xt[off] = a * L[off] + s * noise[off];     // _add_noise guidance_pipeline.py:322
+    }
+}
+
+// phi std(e_c) / std(cfg) + 1 - phi for clip b from ddim_partial_kernel's partials (as ddim_apply_kernel); 1 when off.
+// Block-uniform branch: every thread of the block reaches the barrier or none does.
+__device__ __forceinline__ float sds_rescale_factor(float phi, const float* eu, const float* __restrict__ ws, int b,
+                                                    int64_t n, double* tot) {
+    if (!(phi > 0.f) || !eu) return 1.0f;
+    if (threadIdx.x < 4) {
+        double t = 0.0;
+        for (int k = 0; k < DDIM_BLOCKS; ++k) t += (double)ws[((size_t)b * DDIM_BLOCKS + k) * 4 + threadIdx.x];
+        tot[threadIdx.x] = t;
+    }
+    __syncthreads();
+    const double cnt = (double)n;     // unbiased std per clip, guidance_pipeline.py:352-353
+    const double mean_cfg = tot[0] / cnt, mean_txt = tot[2] / cnt;
+    const double var_cfg = fmax(tot[1] - cnt * mean_cfg * mean_cfg, 0.0) / (cnt - 1.0);
+    const double var_txt = fmax(tot[3] - cnt * mean_txt * mean_txt, 0.0) / (cnt - 1.0);
+    const float ratio = (float)sqrt(var_txt) / (float)sqrt(var_cfg);
+    return phi * ratio + (1.f - phi);
+}
+
+// d = L - x0 of one element: CFG (+ rescale) -> x0 (the reference's eps formula or the v conversion)
+__device__ __forceinline__ float sds_d(const DcSdsParams& p, const DcDdimParams& q, const float* ec, const float* eu,
+                                       size_t eoff, float factor, float xt, float lat, float c1, float c2) {
+#pragma clang fp contract(off)
+    const float e = ddim_cfg(q, ec, eu, nullptr, eoff) * factor;
+    const float x0 = p.x0_param ? c1 * xt - c2 * e : (xt - c2 * e) / c1;   // guidance_pipeline.py:386
+    return lat - x0;
+}
+
+__device__ __forceinline__ float nan_to_num_f(float x) {            // torch.nan_to_num defaults
+    if (isnan(x)) return 0.f;
+    if (isinf(x)) return x > 0.f ? 3.402823466e+38f : -3.402823466e+38f;
+    return x;
+}
+
+__device__ __forceinline__ float block_sum256(float s, float* red) {  // fixed order; red: 4 floats of LDS
+    s = wave_sum(s);
+    const int lane = threadIdx.x & 63, wave = threadIdx.x >> 6;
+    if (lane == 0) red[wave] = s;
+    __syncthreads();
+    return (red[0] + red[1]) + (red[2] + red[3]);
+}
+
+// "ada": per-block partial sums of |d| per clip (same traversal as ddim_partial_kernel: DDIM_BLOCKS blocks per clip)
+__global__ __launch_bounds__(256) void sds_absd_partial_kernel(const DcSdsParams p, const DcDdimParams q,
+                                                               const float* __restrict__ ec,
+                                                               const float* __restrict__ eu, int ld_e,
+                                                               const float* __restrict__ xt,
+                                                               const float* __restrict__ L, int C, int THW,
+                                                               const float* __restrict__ ws,
+                                                               float* __restrict__ ws_abs) {
+    __shared__ double tot[4];
+    __shared__ float red[4];
+    const int b = blockIdx.y, B = gridDim.y;
+    const int64_t n = (int64_t)C * THW;
+    const float factor = sds_rescale_factor(p.guidance_rescale, eu, ws, b, n, tot);
+    const int k = p.step_index ? p.step_index[0] : p.index;
+    const float c1 = p.c1[(size_t)k * B + b], c2 = p.c2[(size_t)k * B + b];
+    float s = 0.f;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)DDIM_BLOCKS * 256) {
+        const int c = (int)(i / THW), pos = (int)(i - (int64_t)c * THW);
+        const size_t xoff = (size_t)b * n + i;
+        s += fabsf(sds_d(p, q, ec, eu, ddim_eoff(q, b, c, pos, C, THW, ld_e), factor, xt[xoff], L[xoff], c1, c2));
+    }
+    s = block_sum256(s, red);
+    if (threadIdx.x == 0) ws_abs[(size_t)b * DDIM_BLOCKS + blockIdx.x] = s;
+}
+
+__global__ __launch_bounds__(256) void sds_apply_kernel(const DcSdsParams p, const DcDdimParams q,
+                                                        const float* __restrict__ ec, const float* __restrict__ eu,
+                                                        int ld_e, const float* __restrict__ xt, float* __restrict__ L,
+                                                        float* __restrict__ m, float* __restrict__ v, int C, int THW,
+                                                        const float* __restrict__ ws,
+                                                        const float* __restrict__ ws_abs,
+                                                        float* __restrict__ ws_loss) {
+#pragma clang fp contract(off)
+    __shared__ double tot[4];
+    __shared__ float red[4];
+    const int b = blockIdx.y, B = gridDim.y;
+    const int64_t n = (int64_t)C * THW;
+    const float factor = sds_rescale_factor(p.guidance_rescale, eu, ws, b, n, tot);
+    const int k = p.step_index ? p.step_index[0] : p.index;
+    const float c1 = p.c1[(size_t)k * B + b], c2 = p.c2[(size_t)k * B + b];
+    // grad = coef d ("t": w(t); "uniform": 1) or d / max(mean|d|, 1e-4) ("ada"), guidance_pipeline.py:389-405
+    const float coef = p.weight_type == 0 ? p.w[(size_t)k * B + b] : 1.f;
+    float wf = 1.f;
+    if (p.weight_type == 1) {
+        double t = 0.0;
+        for (int j = 0; j < DDIM_BLOCKS; ++j) t += (double)ws_abs[(size_t)b * DDIM_BLOCKS + j];
+        wf = (float)(t / (double)n);
+        if (!isnan(wf)) wf = fmaxf(wf, 1e-4f);    // torch.clamp keeps a NaN
+    }
+    const float step = p.step_size[k], bc2 = p.bc2_sqrt[k];
+    const float b2 = p.beta2, omb1 = p.one_minus_beta1, omb2 = p.one_minus_beta2;
+    float acc = 0.f;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int c = (int)(i / THW), pos = (int)(i - (int64_t)c * THW);     // NCTHW order for x_t / L / m / v
+        const size_t xoff = (size_t)b * n + i;
+        float lat = L[xoff];
+        const float d = sds_d(p, q, ec, eu, ddim_eoff(q, b, c, pos, C, THW, ld_e), factor, xt[xoff], lat, c1, c2);
+        const float grad = nan_to_num_f(p.weight_type == 1 ? d / wf : coef * d);
+        acc += grad * grad;
+        // torch.optim.Adam / AdamW (single-tensor): the gradient of 0.5 mse(L, L - grad) / B is grad / (B N)
+        const float g = grad * p.grad_scale;
+        float mv = m[xoff];
+        mv = omb1 < 0.5f ? mv + omb1 * (g - mv) : g - (g - mv) * (1.f - omb1);   // exp_avg.lerp_(g, 1 - beta1)
+        const float vv = v[xoff] * b2 + omb2 * g * g;                            // mul_(beta2).addcmul_(g, g, 1 - beta2)
+        if (p.decay != 1.f) lat = lat * p.decay;                                  // AdamW: param.mul_(1 - lr wd)
+        const float denom = sqrtf(vv) / bc2 + p.eps;
+        L[xoff] = lat - step * (mv / denom);                                      // addcdiv_(m, denom, -step_size)
+        m[xoff] = mv;
+        v[xoff] = vv;
+    }
+    acc = block_sum256(acc, red);
+    if (threadIdx.x == 0) ws_loss[(size_t)b * gridDim.x + blockIdx.x] = acc;
+}
+
+// loss[k] = 0.5 mean(grad^2) / B from the apply pass's `count` partials (fixed order: per-thread strided sums, then a
+// tree), guidance_pipeline.py:420
+__global__ __launch_bounds__(256) void sds_loss_kernel(const DcSdsParams p, const float* __restrict__ ws_loss,
+                                                       int count) {
+    __shared__ double part[256];
+    double s = 0.0;
+    for (int j = threadIdx.x; j < count; j += 256) s += (double)ws_loss[j];
+    part[threadIdx.x] = s;
+    __syncthreads();
+    for (int w = 128; w > 0; w >>= 1) {
+        if ((int)threadIdx.x < w) part[threadIdx.x] += part[threadIdx.x + w];
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        const int k = p.step_index ? p.step_index[0] : p.index;
+        p.loss[k] = (float)(0.5 * part[0] * (double)p.grad_scale);
+    }
+}
+
 
 // dst[c][r] = src[r][c] for bf16 rows; 64x64 tiles through LDS (pad column against bank conflicts)
 __global__ __launch_bounds__(256) void transpose_kernel(const bf16_t* __restrict__ src, int lds_, bf16_t* __restrict__ dst,
@@ -643,6 +800,56 @@ extern "C" int dc_dpmpp_step(const DcDpmParams* pp, const float* e_cond, const f
     hipLaunchKernelGGL(dpmpp_apply_kernel, dim3(grid_for(n, 256, 1024), B), dim3(256), 0, stream, p, q, e_cond, e_uncond,
                        e_img, ld_e, x, noise, x_prev, pred_x0, C, THW, n * B, workspace);
     DC_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dc_sds_noise(const DcSdsParams* pp, const float* latent, const float* noise, float* x_t, int B,
+                            int64_t n_per_clip, void* stream_) {
+    if (!pp || !latent || !noise || !x_t) return DC_ERR_ARG;
+    if (!pp->c1 || !pp->c2) return DC_ERR_ARG;
+    if (B < 1 || n_per_clip < 1) return DC_ERR_SHAPE;
+    hipLaunchKernelGGL(sds_noise_kernel, dim3(grid_for(n_per_clip, 256, 1024), B), dim3(256), 0, (hipStream_t)stream_,
+                       *pp, latent, noise, x_t, n_per_clip);
+    DC_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dc_sds_step(const DcSdsParams* pp, const float* e_cond, const float* e_uncond, int ld_e,
+                           const float* x_t, float* latent, float* m, float* v, int B, int C, int THW, float* workspace,
+                           void* stream_) {
+    if (!pp || !e_cond || !x_t || !latent || !m || !v || !workspace) return DC_ERR_ARG;
+    const DcSdsParams& p = *pp;
+    if (!p.c1 || !p.c2 || !p.step_size || !p.bc2_sqrt) return DC_ERR_ARG;
+    if (p.weight_type < 0 || p.weight_type > 2 || (p.weight_type == 0 && !p.w)) return DC_ERR_ARG;
+    if (B < 1 || C < 1 || THW < 1) return DC_ERR_SHAPE;
+    if (!p.e_nchw && ld_e < C) return DC_ERR_SHAPE;
+    const float* eu = (e_uncond && p.cfg_scale > 1.f) ? e_uncond : nullptr;   // guidance_pipeline.py:374-379
+    DcDdimParams q = {};                      // the CFG fields in the layout ddim_partial_kernel / ddim_cfg read
+    q.cfg_scale = p.cfg_scale;
+    q.e_nchw = p.e_nchw;
+    // workspace: [B][DDIM_BLOCKS][4] rescale partials | [B][DDIM_BLOCKS] |d| partials | [B][<= SDS_APPLY_BLOCKS] grad^2
+    float* ws_abs = workspace + (size_t)B * DDIM_BLOCKS * 4;
+    float* ws_loss = ws_abs + (size_t)B * DDIM_BLOCKS;
+    hipStream_t stream = (hipStream_t)stream_;
+    if (p.guidance_rescale > 0.f && eu) {
+        hipLaunchKernelGGL(ddim_partial_kernel, dim3(DDIM_BLOCKS, B), dim3(256), 0, stream, q, e_cond, eu, nullptr,
+                           ld_e, C, THW, workspace);
+        DC_CHECK_LAUNCH();
+    }
+    if (p.weight_type == 1) {
+        hipLaunchKernelGGL(sds_absd_partial_kernel, dim3(DDIM_BLOCKS, B), dim3(256), 0, stream, p, q, e_cond, eu, ld_e,
+                           x_t, latent, C, THW, workspace, ws_abs);
+        DC_CHECK_LAUNCH();
+    }
+    const int64_t n = (int64_t)C * THW;
+    const int nblk = grid_for(n, 256, SDS_APPLY_BLOCKS);
+    hipLaunchKernelGGL(sds_apply_kernel, dim3(nblk, B), dim3(256), 0, stream, p, q, e_cond, eu, ld_e, x_t, latent, m, v,
+                       C, THW, workspace, ws_abs, ws_loss);
+    DC_CHECK_LAUNCH();
+    if (p.loss) {
+        hipLaunchKernelGGL(sds_loss_kernel, dim3(1), dim3(256), 0, stream, p, ws_loss, nblk * B);
+        DC_CHECK_LAUNCH();
+    }
     return 0;
 }
 

@@ -749,6 +749,77 @@ def dpmpp_step(tables, e_cond, e_uncond, e_img, x, noise, x_prev, pred_x0, works
     return x_prev, pred_x0
 
 
+SDS_WEIGHT_TYPES = ("t", "ada", "uniform")
+SDS_X0_FORMULAS = ("reference", "parameterization")
+
+
+def _sds_params(tables, B, step_index, index, noise_step_stride=0, weight_type="t", x0_formula="reference", e_nchw=False,
+                cfg_scale=1.0, guidance_rescale=0.0, betas=(0.9, 0.999), eps=1e-8, decay=1.0, grad_scale=1.0, loss=None):
+    if weight_type not in SDS_WEIGHT_TYPES:
+        raise ValueError(f"weight_type must be one of {SDS_WEIGHT_TYPES}, got {weight_type!r}")
+    if x0_formula not in SDS_X0_FORMULAS:
+        raise ValueError(f"x0_formula must be one of {SDS_X0_FORMULAS}, got {x0_formula!r}")
+    # the kernels read entry [k * B + b] of the per-clip tables and [k] of the per-step ones, k < steps
+    steps = int(tables["step_size"].numel()) if step_index is not None else index + 1
+    for k in ("c1", "c2", "w"):
+        _need(tables.get(k), steps * B, k)
+    for k in ("step_size", "bc2_sqrt"):
+        _need(tables.get(k), steps, k)
+    _need(loss, steps, "loss")
+    p = _hip.DcSdsParams()
+    for k in ("c1", "c2", "w", "step_size", "bc2_sqrt"):
+        t = tables.get(k)
+        setattr(p, k, 0 if t is None else t.data_ptr())
+    p.step_index = 0 if step_index is None else step_index.data_ptr()
+    p.index, p.weight_type = index, SDS_WEIGHT_TYPES.index(weight_type)
+    p.x0_param, p.e_nchw = SDS_X0_FORMULAS.index(x0_formula), 1 if e_nchw else 0
+    p.cfg_scale, p.guidance_rescale = cfg_scale, guidance_rescale
+    p.beta2, p.eps = betas[1], eps
+    p.one_minus_beta1, p.one_minus_beta2 = 1.0 - betas[0], 1.0 - betas[1]     # float64, then fp32: as torch.optim
+    p.decay, p.grad_scale = decay, grad_scale
+    p.noise_step_stride = noise_step_stride
+    p.loss = 0 if loss is None else loss.data_ptr()
+    return p
+
+
+def sds_noise(tables, latent, noise, x_t, *, B, index=0, step_index=None, noise_step_stride=0):
+    """x_t = c1 latent + c2 noise (dc_sds_noise) per clip; tables: fp32 device c1, c2 [S*B] (+ step_size [S] with a
+    step counter). With step_index, step k's noise starts at noise + k * noise_step_stride."""
+    n = latent.numel()
+    _need(x_t, n, "x_t")
+    if step_index is not None:
+        _need(noise, (int(tables["step_size"].numel()) - 1) * noise_step_stride + n, "noise")
+    else:
+        _need(noise, n, "noise")
+    p = _sds_params(tables, B, step_index, index, noise_step_stride)
+    check(_hip.lib().dc_sds_noise(C.byref(p), _ptr(latent), _ptr(noise), _ptr(x_t), B, n // B, stream_ptr()),
+          "dc_sds_noise")
+    return x_t
+
+
+def sds_step(tables, e_cond, e_uncond, x_t, latent, m, v, workspace, loss=None, *, B, Cc, THW, index=0, step_index=None,
+             weight_type="t", x0_formula="reference", cfg_scale=1.0, guidance_rescale=0.0, betas=(0.9, 0.999), eps=1e-8,
+             decay=1.0, grad_scale=None, e_nchw=False, ld_e=None):
+    """One SDS gradient + Adam(W) step on `latent` in place (dc_sds_step). tables: fp32 device vectors c1, c2, w [S*B]
+    and step_size, bc2_sqrt [S] (samplers/sds.py); m, v: the moments; loss: [S] fp32 or None. grad_scale defaults to
+    1 / (B * numel(latent)), the gradient of 0.5 mse / B."""
+    n = B * Cc * THW
+    for t, nm in ((x_t, "x_t"), (latent, "latent"), (m, "m"), (v, "v")):
+        _need(t, n, nm)
+    _need(workspace, 16 * B * 256, "workspace")
+    if ld_e is None:
+        ld_e = 0 if e_nchw else e_cond.stride(0)
+    for t, nm in ((e_cond, "e_cond"), (e_uncond, "e_uncond")):
+        _need(t, n if e_nchw else (B * THW - 1) * ld_e + Cc, nm)
+    if grad_scale is None:
+        grad_scale = 1.0 / (B * n)
+    p = _sds_params(tables, B, step_index, index, 0, weight_type, x0_formula, e_nchw, cfg_scale, guidance_rescale,
+                    betas, eps, decay, grad_scale, loss)
+    check(_hip.lib().dc_sds_step(C.byref(p), _ptr(e_cond), _ptr(e_uncond), ld_e, _ptr(x_t), _ptr(latent), _ptr(m),
+                                 _ptr(v), B, Cc, THW, _ptr(workspace), stream_ptr()), "dc_sds_step")
+    return latent
+
+
 def mask_blend(img, x0, mask, qnoise, tables, *, index=0, step_index=None, clean=False, noise_step_stride=0):
     """img = orig*mask + (1-mask)*img in place, orig = x0 or its q_sample at the step's timestep (fp32, same shapes)."""
     n = img.numel()

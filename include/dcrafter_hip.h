@@ -244,6 +244,45 @@ int dc_dpmpp_step(const DcDpmParams* p, const float* e_cond, const float* e_unco
                   const float* x, const float* noise, float* x_prev, float* pred_x0, int B, int C, int THW,
                   float* workspace, void* stream);
 
+typedef struct DcSdsParams {
+    /* per-step fp32 tables, indexed by k = step_index[0] (device) when step_index != NULL, else by `index`; host-side
+     * values as torch computes them (samplers/sds.py). Per clip b: entry [k * B + b]. */
+    const float* c1;             /* [S][B] sqrt(alphas_cumprod[t]) */
+    const float* c2;             /* [S][B] sqrt(1 - alphas_cumprod[t]) */
+    const float* w;              /* [S][B] 1 - alphas_cumprod[t] ("t" weighting; may be NULL otherwise) */
+    const float* step_size;      /* [S] lr / (1 - beta1^n), n = k + 1 */
+    const float* bc2_sqrt;       /* [S] sqrt(1 - beta2^n) */
+    const int32_t* step_index;   /* device counter or NULL */
+    int index;
+    int weight_type;             /* 0 "t": w d, 1 "ada": d / max(mean|d|, 1e-4) per clip, 2 "uniform": d */
+    int x0_param;                /* 0: x0 = (x_t - c2 e) / c1 (the reference's formula), 1: x0 = c1 x_t - c2 e (v) */
+    int e_nchw;                  /* as DcDdimParams */
+    float cfg_scale;             /* CFG applied when e_uncond != NULL and cfg_scale > 1 */
+    float guidance_rescale;      /* 0 -> off */
+    float beta2, eps;            /* Adam's beta2 and eps */
+    float one_minus_beta1;       /* 1 - beta1 and 1 - beta2, rounded from double as torch.optim rounds them */
+    float one_minus_beta2;
+    float decay;                 /* 1 - lr * weight_decay (AdamW), 1 (Adam) */
+    float grad_scale;            /* 1 / (B * N), N = numel(latent): the gradient of 0.5 mse / B */
+    int64_t noise_step_stride;   /* dc_sds_noise with step_index: noise for step k starts at noise + k * stride */
+    float* loss;                 /* [S] fp32: loss[k] = 0.5 mean(grad^2) / B; NULL -> not written */
+} DcSdsParams;
+
+/* SDS noising pass: x_t[b] = c1[k,b] latent[b] + c2[k,b] noise[k] for B clips of n_per_clip fp32 elements each.
+ * latent is not written. replaces: DynamiCrafterGuidancePipeline._add_noise guidance_pipeline.py:304-324 */
+int dc_sds_noise(const DcSdsParams* p, const float* latent, const float* noise, float* x_t, int B, int64_t n_per_clip,
+                 void* stream);
+
+/* SDS gradient + Adam / AdamW step on the latent [B, C, T*HW] fp32 in place, with its moments m, v (same shape).
+ * e_cond / e_uncond are the UNet outputs as in dc_ddim_step (channels-last rows unless p->e_nchw; e_uncond may be
+ * NULL); x_t is the noised latent of dc_sds_noise. Per element: e = CFG [+ guidance rescale], x0, d = latent - x0,
+ * grad = nan_to_num(weight(d)), g = grad_scale grad, then torch.optim.Adam(W)'s update with n = k + 1; loss[k] gets
+ * 0.5 sum(grad^2) grad_scale. workspace: >= 16 * B * 256 floats.
+ * replaces: DynamiCrafterGuidancePipeline._sds_loss + _apply_guidance_rescale guidance_pipeline.py:326-424 and the
+ * loss.backward() / optimizer.step() of _optimization_loop :759-808 */
+int dc_sds_step(const DcSdsParams* p, const float* e_cond, const float* e_uncond, int ld_e, const float* x_t,
+                float* latent, float* m, float* v, int B, int C, int THW, float* workspace, void* stream);
+
 /* DynamiCrafter's dual cross-attention in one launch: o = softmax(s q k^T) v + scale2 * softmax(s q k2^T) v2 with two
  * independent softmaxes (text keys Lk, image keys Lk2) over the same queries; head_dim 64. q/o rows as in
  * dc_flash_attn_d64; k, v, k2, v2 rows share the stride ldkv and the batch stride kv_bstride (views into one fused
