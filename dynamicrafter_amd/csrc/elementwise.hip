@@ -244,12 +244,23 @@ __global__ void vae_sample_kernel(const bf16_t* __restrict__ mom, int ld, const 
 // order, then applies guidance rescale, v->eps/x0, dynamic rescale and the DDIM step elementwise.
 constexpr int DDIM_BLOCKS = 256;   // partial blocks per sample
 
-__device__ __forceinline__ size_t ddim_eoff(const DcDdimParams& p, int b, int c, int pos, int C, int THW, int ld_e) {
+// What ddim_partial_kernel / ddim_cfg / ddim_eoff read of a step's parameters, from any of the three structs.
+struct CfgArgs { float cfg_scale, cfg_img; int e_nchw; };
+__host__ __device__ inline float cfg_img_of(const DcSdsParams&) { return 0.f; }   // SDS has no image-only branch
+template <class P> __host__ __device__ inline float cfg_img_of(const P& p) { return p.cfg_img; }
+template <class P> __host__ __device__ inline CfgArgs cfg_args(const P& p) {
+    return {p.cfg_scale, cfg_img_of(p), p.e_nchw};
+}
+
+// the step a launch works on: the device counter when there is one, else the host's index
+template <class P> __device__ __forceinline__ int step_idx(const P& p) { return p.step_index ? p.step_index[0] : p.index; }
+
+__device__ __forceinline__ size_t ddim_eoff(const CfgArgs& p, int b, int c, int pos, int C, int THW, int ld_e) {
     // channels-last rows [b][pos][ld_e] (UNet row output) or the reference's [b][c][pos] layout
     return p.e_nchw ? ((size_t)b * C + c) * THW + pos : ((size_t)b * THW + pos) * ld_e + c;
 }
 
-__device__ __forceinline__ float ddim_cfg(const DcDdimParams& p, const float* ec, const float* eu, const float* ei,
+__device__ __forceinline__ float ddim_cfg(const CfgArgs& p, const float* ec, const float* eu, const float* ei,
                                           size_t off) {
     const float c = ec[off];
     if (!eu) return c;
@@ -272,7 +283,7 @@ __device__ __forceinline__ float ddim_dir_coef(float a_prev, float sigma) {
     return sqrtf(fmaxf(r, 0.f));
 }
 
-__global__ __launch_bounds__(256) void ddim_partial_kernel(const DcDdimParams p, const float* __restrict__ ec,
+__global__ __launch_bounds__(256) void ddim_partial_kernel(const CfgArgs p, const float* __restrict__ ec,
                                                            const float* __restrict__ eu, const float* __restrict__ ei,
                                                            int ld_e, int C, int THW, float* __restrict__ ws) {
     __shared__ float red[4][4];
@@ -296,6 +307,27 @@ __global__ __launch_bounds__(256) void ddim_partial_kernel(const DcDdimParams p,
     }
 }
 
+// Guidance rescale: phi std(e_c) / std(cfg) + 1 - phi for clip b from ddim_partial_kernel's partials, re-reduced in a
+// fixed order by every workgroup; 1 when off. cfg * factor = cfg * (phi*std_text/std_cfg + 1 - phi).
+// Block-uniform branch: every thread of the block reaches the barrier or none does. tot: 4 doubles of LDS.
+__device__ __forceinline__ float rescale_factor(float phi, const float* eu, const float* __restrict__ ws, int b,
+                                                int64_t n, double* tot) {
+    if (!(phi > 0.f) || !eu) return 1.0f;
+    if (threadIdx.x < 4) {
+        double t = 0.0;
+        for (int k = 0; k < DDIM_BLOCKS; ++k) t += (double)ws[((size_t)b * DDIM_BLOCKS + k) * 4 + threadIdx.x];
+        tot[threadIdx.x] = t;
+    }
+    __syncthreads();
+    const double cnt = (double)n;
+    // unbiased std (torch.std default) per clip, utils_diffusion.py:152-153 / guidance_pipeline.py:352-353
+    const double mean_cfg = tot[0] / cnt, mean_txt = tot[2] / cnt;
+    const double var_cfg = fmax(tot[1] - cnt * mean_cfg * mean_cfg, 0.0) / (cnt - 1.0);
+    const double var_txt = fmax(tot[3] - cnt * mean_txt * mean_txt, 0.0) / (cnt - 1.0);
+    const float ratio = (float)sqrt(var_txt) / (float)sqrt(var_cfg);
+    return phi * ratio + (1.f - phi);
+}
+
 __global__ __launch_bounds__(256) void ddim_apply_kernel(const DcDdimParams p, const float* __restrict__ ec,
                                                          const float* __restrict__ eu, const float* __restrict__ ei,
                                                          int ld_e, const float* x,      // x and x_prev may alias: the
@@ -305,23 +337,9 @@ __global__ __launch_bounds__(256) void ddim_apply_kernel(const DcDdimParams p, c
     __shared__ double tot[4];
     const int b = blockIdx.y;
     const int64_t n = (int64_t)C * THW;
-    float factor = 1.0f;   // guidance rescale: cfg * (phi*std_text/std_cfg + 1 - phi)
-    if (p.guidance_rescale > 0.f && eu) {
-        if (threadIdx.x < 4) {
-            double t = 0.0;
-            for (int k = 0; k < DDIM_BLOCKS; ++k) t += (double)ws[((size_t)b * DDIM_BLOCKS + k) * 4 + threadIdx.x];
-            tot[threadIdx.x] = t;
-        }
-        __syncthreads();
-        const double cnt = (double)n;
-        // unbiased std (torch.std default), utils_diffusion.py:152-153
-        const double mean_cfg = tot[0] / cnt, mean_txt = tot[2] / cnt;
-        const double var_cfg = fmax(tot[1] - cnt * mean_cfg * mean_cfg, 0.0) / (cnt - 1.0);
-        const double var_txt = fmax(tot[3] - cnt * mean_txt * mean_txt, 0.0) / (cnt - 1.0);
-        const float ratio = (float)sqrt(var_txt) / (float)sqrt(var_cfg);
-        factor = p.guidance_rescale * ratio + (1.f - p.guidance_rescale);
-    }
-    const int idx = p.step_index ? p.step_index[0] : p.index;
+    const CfgArgs q = cfg_args(p);
+    const float factor = rescale_factor(p.guidance_rescale, eu, ws, b, n, tot);
+    const int idx = step_idx(p);
     if (noise && p.step_index) noise += (size_t)idx * p.noise_step_stride;
     const float a_t = p.a_t[idx], a_prev = p.a_prev[idx], sigma = p.sigma_t[idx], s1m = p.sqrt_one_minus_at[idx];
     const float sq_acp = p.v_param ? p.sqrt_acp_t[idx] : 0.f;
@@ -335,9 +353,9 @@ __global__ __launch_bounds__(256) void ddim_apply_kernel(const DcDdimParams p, c
     const float dir_coef = ddim_dir_coef(a_prev, sigma);
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
         const int c = (int)(i / THW), pos = (int)(i - (int64_t)c * THW);     // NCTHW order for x / outputs
-        const size_t eoff = ddim_eoff(p, b, c, pos, C, THW, ld_e);
+        const size_t eoff = ddim_eoff(q, b, c, pos, C, THW, ld_e);
         const size_t xoff = (size_t)b * n + i;
-        const float mo = ddim_cfg(p, ec, eu, ei, eoff) * factor;
+        const float mo = ddim_cfg(q, ec, eu, ei, eoff) * factor;
         const float xv = x[xoff];
         float e_t, px0;
         if (p.v_param) {
@@ -356,11 +374,11 @@ __global__ __launch_bounds__(256) void ddim_apply_kernel(const DcDdimParams p, c
 
 // ---------------------------------------------------------------------------------------------------------
 // DPM-Solver++ 2M / 2M SDE update (data-prediction multistep form). The guidance-rescale statistics come from
-// ddim_partial_kernel (same workspace layout, same fixed reduction order), launched with a DcDdimParams `q` that
-// carries the CFG fields; this one pass converts the model output to the raw x0_i, forms
-// D = (1 + k) x0_i - k x0_{i-1} with x0_{i-1} from the history ring, and writes x_prev, pred_x0 = r x0_i and x0_i.
+// ddim_partial_kernel (same workspace layout, same fixed reduction order); this one pass converts the model output to
+// the raw x0_i, forms D = (1 + k) x0_i - k x0_{i-1} with x0_{i-1} from the history ring, and writes x_prev,
+// pred_x0 = r x0_i and x0_i.
 // Per element: e_c, e_u [, e_i], x, x0_{i-1}, noise in; x_prev, pred_x0, x0_i out.
-__global__ __launch_bounds__(256) void dpmpp_apply_kernel(const DcDpmParams p, const DcDdimParams q,
+__global__ __launch_bounds__(256) void dpmpp_apply_kernel(const DcDpmParams p,
                                                           const float* __restrict__ ec, const float* __restrict__ eu,
                                                           const float* __restrict__ ei, int ld_e,
                                                           const float* x,      // x and x_prev may alias (in place)
@@ -370,22 +388,9 @@ __global__ __launch_bounds__(256) void dpmpp_apply_kernel(const DcDpmParams p, c
     __shared__ double tot[4];
     const int b = blockIdx.y;
     const int64_t n = (int64_t)C * THW;
-    float factor = 1.0f;   // guidance rescale, as ddim_apply_kernel
-    if (p.guidance_rescale > 0.f && eu) {
-        if (threadIdx.x < 4) {
-            double t = 0.0;
-            for (int k = 0; k < DDIM_BLOCKS; ++k) t += (double)ws[((size_t)b * DDIM_BLOCKS + k) * 4 + threadIdx.x];
-            tot[threadIdx.x] = t;
-        }
-        __syncthreads();
-        const double cnt = (double)n;
-        const double mean_cfg = tot[0] / cnt, mean_txt = tot[2] / cnt;
-        const double var_cfg = fmax(tot[1] - cnt * mean_cfg * mean_cfg, 0.0) / (cnt - 1.0);
-        const double var_txt = fmax(tot[3] - cnt * mean_txt * mean_txt, 0.0) / (cnt - 1.0);
-        const float ratio = (float)sqrt(var_txt) / (float)sqrt(var_cfg);
-        factor = p.guidance_rescale * ratio + (1.f - p.guidance_rescale);
-    }
-    const int idx = p.step_index ? p.step_index[0] : p.index;
+    const CfgArgs q = cfg_args(p);
+    const float factor = rescale_factor(p.guidance_rescale, eu, ws, b, n, tot);
+    const int idx = step_idx(p);
     if (noise && p.step_index) noise += (size_t)idx * p.noise_step_stride;
     const float A = p.A[idx], al_t = p.alpha_t[idx], al_pr = p.alpha_p_r[idx], kk = p.k[idx];
     const float ncoef = p.N ? p.N[idx] * p.temperature : 0.f;
@@ -415,18 +420,21 @@ __global__ __launch_bounds__(256) void dpmpp_apply_kernel(const DcDpmParams p, c
 
 // ---------------------------------------------------------------------------------------------------------
 // Score distillation (SDS) with an Adam / AdamW step on the latent. The noising pass writes x_t = c1 L + c2 eps[k].
-// The update reuses ddim_partial_kernel for the guidance-rescale statistics (launched with a DcDdimParams `q` that
-// carries the CFG fields); "ada" adds one per-clip reduction of |d|; sds_apply_kernel forms the gradient, updates
-// m, v and L in place and leaves per-block partial sums of grad^2, which sds_loss_kernel reduces in a fixed order.
+// The update reuses ddim_partial_kernel for the guidance-rescale statistics; "ada" adds one per-clip reduction of |d|;
+// sds_apply_kernel forms the gradient, updates m, v and L in place and leaves per-block partial sums of grad^2, which
+// sds_loss_kernel reduces in a fixed order.
 // Every step of torch's arithmetic is rounded separately, as torch evaluates it: no FMA contraction here.
 constexpr int SDS_APPLY_BLOCKS = 1024;   // cap on apply-pass blocks per clip (= loss partials per clip)
+// per clip, dc_sds_step carves the largest layout of the three entry points out of the step workspace: it must fit
+// the 16 * 256 floats include/dcrafter_hip.h documents and ops.step_workspace allocates
+static_assert((4 + 1) * DDIM_BLOCKS + SDS_APPLY_BLOCKS <= 16 * 256, "step workspace layout exceeds its documented size");
 
 __global__ __launch_bounds__(256) void sds_noise_kernel(const DcSdsParams p, const float* __restrict__ L,
                                                         const float* __restrict__ noise, float* __restrict__ xt,
                                                         int64_t n) {
 #pragma clang fp contract(off)
     const int b = blockIdx.y, B = gridDim.y;
-    const int k = p.step_index ? p.step_index[0] : p.index;
+    const int k = step_idx(p);
     if (p.step_index) noise += (size_t)k * p.noise_step_stride;
     const float a = p.c1[(size_t)k * B + b], s = p.c2[(size_t)k * B + b];
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
@@ -435,27 +443,8 @@ __global__ __launch_bounds__(256) void sds_noise_kernel(const DcSdsParams p, con
     }
 }
 
-// phi std(e_c) / std(cfg) + 1 - phi for clip b from ddim_partial_kernel's partials (as ddim_apply_kernel); 1 when off.
-// Block-uniform branch: every thread of the block reaches the barrier or none does.
-__device__ __forceinline__ float sds_rescale_factor(float phi, const float* eu, const float* __restrict__ ws, int b,
-                                                    int64_t n, double* tot) {
-    if (!(phi > 0.f) || !eu) return 1.0f;
-    if (threadIdx.x < 4) {
-        double t = 0.0;
-        for (int k = 0; k < DDIM_BLOCKS; ++k) t += (double)ws[((size_t)b * DDIM_BLOCKS + k) * 4 + threadIdx.x];
-        tot[threadIdx.x] = t;
-    }
-    __syncthreads();
-    const double cnt = (double)n;     // unbiased std per clip, guidance_pipeline.py:352-353
-    const double mean_cfg = tot[0] / cnt, mean_txt = tot[2] / cnt;
-    const double var_cfg = fmax(tot[1] - cnt * mean_cfg * mean_cfg, 0.0) / (cnt - 1.0);
-    const double var_txt = fmax(tot[3] - cnt * mean_txt * mean_txt, 0.0) / (cnt - 1.0);
-    const float ratio = (float)sqrt(var_txt) / (float)sqrt(var_cfg);
-    return phi * ratio + (1.f - phi);
-}
-
 // d = L - x0 of one element: CFG (+ rescale) -> x0 (the reference's eps formula or the v conversion)
-__device__ __forceinline__ float sds_d(const DcSdsParams& p, const DcDdimParams& q, const float* ec, const float* eu,
+__device__ __forceinline__ float sds_d(const DcSdsParams& p, const CfgArgs& q, const float* ec, const float* eu,
                                        size_t eoff, float factor, float xt, float lat, float c1, float c2) {
 #pragma clang fp contract(off)
     const float e = ddim_cfg(q, ec, eu, nullptr, eoff) * factor;
@@ -478,7 +467,7 @@ __device__ __forceinline__ float block_sum256(float s, float* red) {  // fixed o
 }
 
 // "ada": per-block partial sums of |d| per clip (same traversal as ddim_partial_kernel: DDIM_BLOCKS blocks per clip)
-__global__ __launch_bounds__(256) void sds_absd_partial_kernel(const DcSdsParams p, const DcDdimParams q,
+__global__ __launch_bounds__(256) void sds_absd_partial_kernel(const DcSdsParams p,
                                                                const float* __restrict__ ec,
                                                                const float* __restrict__ eu, int ld_e,
                                                                const float* __restrict__ xt,
@@ -489,8 +478,9 @@ __global__ __launch_bounds__(256) void sds_absd_partial_kernel(const DcSdsParams
     __shared__ float red[4];
     const int b = blockIdx.y, B = gridDim.y;
     const int64_t n = (int64_t)C * THW;
-    const float factor = sds_rescale_factor(p.guidance_rescale, eu, ws, b, n, tot);
-    const int k = p.step_index ? p.step_index[0] : p.index;
+    const CfgArgs q = cfg_args(p);
+    const float factor = rescale_factor(p.guidance_rescale, eu, ws, b, n, tot);
+    const int k = step_idx(p);
     const float c1 = p.c1[(size_t)k * B + b], c2 = p.c2[(size_t)k * B + b];
     float s = 0.f;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)DDIM_BLOCKS * 256) {
@@ -502,7 +492,7 @@ __global__ __launch_bounds__(256) void sds_absd_partial_kernel(const DcSdsParams
     if (threadIdx.x == 0) ws_abs[(size_t)b * DDIM_BLOCKS + blockIdx.x] = s;
 }
 
-__global__ __launch_bounds__(256) void sds_apply_kernel(const DcSdsParams p, const DcDdimParams q,
+__global__ __launch_bounds__(256) void sds_apply_kernel(const DcSdsParams p,
                                                         const float* __restrict__ ec, const float* __restrict__ eu,
                                                         int ld_e, const float* __restrict__ xt, float* __restrict__ L,
                                                         float* __restrict__ m, float* __restrict__ v, int C, int THW,
@@ -514,8 +504,9 @@ __global__ __launch_bounds__(256) void sds_apply_kernel(const DcSdsParams p, con
     __shared__ float red[4];
     const int b = blockIdx.y, B = gridDim.y;
     const int64_t n = (int64_t)C * THW;
-    const float factor = sds_rescale_factor(p.guidance_rescale, eu, ws, b, n, tot);
-    const int k = p.step_index ? p.step_index[0] : p.index;
+    const CfgArgs q = cfg_args(p);
+    const float factor = rescale_factor(p.guidance_rescale, eu, ws, b, n, tot);
+    const int k = step_idx(p);
     const float c1 = p.c1[(size_t)k * B + b], c2 = p.c2[(size_t)k * B + b];
     // grad = coef d ("t": w(t); "uniform": 1) or d / max(mean|d|, 1e-4) ("ada"), guidance_pipeline.py:389-405
     const float coef = p.weight_type == 0 ? p.w[(size_t)k * B + b] : 1.f;
@@ -565,7 +556,7 @@ __global__ __launch_bounds__(256) void sds_loss_kernel(const DcSdsParams p, cons
         __syncthreads();
     }
     if (threadIdx.x == 0) {
-        const int k = p.step_index ? p.step_index[0] : p.index;
+        const int k = step_idx(p);
         p.loss[k] = (float)(0.5 * part[0] * (double)p.grad_scale);
     }
 }
@@ -762,8 +753,8 @@ extern "C" int dc_ddim_step(const DcDdimParams* pp, const float* e_cond, const f
     if (B < 1 || C < 1 || THW < 1) return DC_ERR_SHAPE;
     hipStream_t stream = (hipStream_t)stream_;
     if (p.guidance_rescale > 0.f && e_uncond) {
-        hipLaunchKernelGGL(ddim_partial_kernel, dim3(DDIM_BLOCKS, B), dim3(256), 0, stream, p, e_cond, e_uncond, e_img,
-                           ld_e, C, THW, workspace);
+        hipLaunchKernelGGL(ddim_partial_kernel, dim3(DDIM_BLOCKS, B), dim3(256), 0, stream, cfg_args(p), e_cond, e_uncond,
+                           e_img, ld_e, C, THW, workspace);
         DC_CHECK_LAUNCH();
     }
     const int64_t n = (int64_t)C * THW;
@@ -784,20 +775,14 @@ extern "C" int dc_dpmpp_step(const DcDpmParams* pp, const float* e_cond, const f
     if (e_img && !e_uncond) return DC_ERR_ARG;
     if (B < 1 || C < 1 || THW < 1) return DC_ERR_SHAPE;
     if (!p.e_nchw && ld_e < C) return DC_ERR_SHAPE;
-    // the CFG fields in the layout ddim_partial_kernel / ddim_cfg / ddim_eoff read
-    DcDdimParams q = {};
-    q.cfg_scale = p.cfg_scale;
-    q.cfg_img = p.cfg_img;
-    q.guidance_rescale = p.guidance_rescale;
-    q.e_nchw = p.e_nchw;
     hipStream_t stream = (hipStream_t)stream_;
     if (p.guidance_rescale > 0.f && e_uncond) {
-        hipLaunchKernelGGL(ddim_partial_kernel, dim3(DDIM_BLOCKS, B), dim3(256), 0, stream, q, e_cond, e_uncond, e_img,
-                           ld_e, C, THW, workspace);
+        hipLaunchKernelGGL(ddim_partial_kernel, dim3(DDIM_BLOCKS, B), dim3(256), 0, stream, cfg_args(p), e_cond, e_uncond,
+                           e_img, ld_e, C, THW, workspace);
         DC_CHECK_LAUNCH();
     }
     const int64_t n = (int64_t)C * THW;
-    hipLaunchKernelGGL(dpmpp_apply_kernel, dim3(grid_for(n, 256, 1024), B), dim3(256), 0, stream, p, q, e_cond, e_uncond,
+    hipLaunchKernelGGL(dpmpp_apply_kernel, dim3(grid_for(n, 256, 1024), B), dim3(256), 0, stream, p, e_cond, e_uncond,
                        e_img, ld_e, x, noise, x_prev, pred_x0, C, THW, n * B, workspace);
     DC_CHECK_LAUNCH();
     return 0;
@@ -824,26 +809,23 @@ extern "C" int dc_sds_step(const DcSdsParams* pp, const float* e_cond, const flo
     if (B < 1 || C < 1 || THW < 1) return DC_ERR_SHAPE;
     if (!p.e_nchw && ld_e < C) return DC_ERR_SHAPE;
     const float* eu = (e_uncond && p.cfg_scale > 1.f) ? e_uncond : nullptr;   // guidance_pipeline.py:374-379
-    DcDdimParams q = {};                      // the CFG fields in the layout ddim_partial_kernel / ddim_cfg read
-    q.cfg_scale = p.cfg_scale;
-    q.e_nchw = p.e_nchw;
     // workspace: [B][DDIM_BLOCKS][4] rescale partials | [B][DDIM_BLOCKS] |d| partials | [B][<= SDS_APPLY_BLOCKS] grad^2
     float* ws_abs = workspace + (size_t)B * DDIM_BLOCKS * 4;
     float* ws_loss = ws_abs + (size_t)B * DDIM_BLOCKS;
     hipStream_t stream = (hipStream_t)stream_;
     if (p.guidance_rescale > 0.f && eu) {
-        hipLaunchKernelGGL(ddim_partial_kernel, dim3(DDIM_BLOCKS, B), dim3(256), 0, stream, q, e_cond, eu, nullptr,
-                           ld_e, C, THW, workspace);
+        hipLaunchKernelGGL(ddim_partial_kernel, dim3(DDIM_BLOCKS, B), dim3(256), 0, stream, cfg_args(p), e_cond, eu,
+                           nullptr, ld_e, C, THW, workspace);
         DC_CHECK_LAUNCH();
     }
     if (p.weight_type == 1) {
-        hipLaunchKernelGGL(sds_absd_partial_kernel, dim3(DDIM_BLOCKS, B), dim3(256), 0, stream, p, q, e_cond, eu, ld_e,
+        hipLaunchKernelGGL(sds_absd_partial_kernel, dim3(DDIM_BLOCKS, B), dim3(256), 0, stream, p, e_cond, eu, ld_e,
                            x_t, latent, C, THW, workspace, ws_abs);
         DC_CHECK_LAUNCH();
     }
     const int64_t n = (int64_t)C * THW;
     const int nblk = grid_for(n, 256, SDS_APPLY_BLOCKS);
-    hipLaunchKernelGGL(sds_apply_kernel, dim3(nblk, B), dim3(256), 0, stream, p, q, e_cond, eu, ld_e, x_t, latent, m, v,
+    hipLaunchKernelGGL(sds_apply_kernel, dim3(nblk, B), dim3(256), 0, stream, p, e_cond, eu, ld_e, x_t, latent, m, v,
                        C, THW, workspace, ws_abs, ws_loss);
     DC_CHECK_LAUNCH();
     if (p.loss) {

@@ -22,48 +22,114 @@ from .... import _hip, ops
 from ..utils_diffusion import make_ddim_sampling_parameters, make_ddim_timesteps
 
 
-class FusedRun:
-    """State of one fused sampling run: the latent (updated in place), device tables / counter, the batched
-    guidance branches, and optionally the captured hipGraph of a step. `step()` advances the device-side DDIM
-    index by one; after `S` steps `rewind()` starts the next clip."""
+def _step_inputs(img, S, noises, mask, x0, q_noises, clean_cond):
+    """The per-step draws and the mask operands as the kernels read them, checked in this one place for the fused and
+    the generic path: fp32 on the latent's device, `noises` / `q_noises` long enough for S steps, x0 / mask expanded to
+    the latent's shape. Returns (noises, blend); blend is None without a mask."""
+    f32 = lambda t: t.to(device=img.device, dtype=torch.float32)
+    # mask / x0 blending ahead of every step (ddim.py:174-180): the original latent, re-noised to the step's timestep
+    # with pre-drawn q_sample noise [S, ...] unless clean_cond
+    blend = None
+    if mask is not None:
+        assert x0 is not None
+        if not clean_cond and q_noises is None:
+            q_noises = torch.randn((S,) + tuple(img.shape), device=img.device)
+        blend = dict(x0=f32(x0).expand_as(img).contiguous(), mask=f32(mask).expand_as(img).contiguous(),
+                     clean=bool(clean_cond), q=None if clean_cond else f32(q_noises).contiguous())
+    if noises is not None:
+        noises = f32(noises).contiguous()
+    for name, t in (("noises", noises), ("q_noises", blend and blend["q"])):
+        if t is not None and t.numel() < S * img.numel():
+            raise ValueError(f"{name}: the step kernels read step index * {img.numel()} + i for {S} steps; "
+                             f"got {t.numel()} elements")
+    return noises, blend
+
+
+def _update_kw(m, x, cfg_scale, cfg_img, guidance_rescale, temperature, **extra):
+    """The keyword arguments ops.ddim_step and ops.dpmpp_step share, for a latent x [B, C, ...]."""
+    return dict(B=x.shape[0], Cc=x.shape[1], THW=int(np.prod(x.shape[2:])), v_param=m.parameterization == "v",
+                cfg_scale=cfg_scale, cfg_img=cfg_scale if cfg_img is None else cfg_img,
+                guidance_rescale=guidance_rescale, temperature=temperature, **extra)
+
+
+class StepRun:
+    """What every fused run owns: the latent `img` (updated in place), the batched guidance branches, the step
+    workspace, the device step counter with the [S, nb*B] timestep table it indexes, and optionally the captured
+    hipGraph of a step. A subclass supplies `_enqueue()`, the launches of one step (no allocation, no host sync,
+    ending in ops.advance_counter), and `_reset_state()`, which puts back whatever else a step changes besides the
+    latent and the counter. `step()` advances the device counter by one; after `S` steps `rewind()` starts over."""
+
+    def __init__(self, model, img, branches, t_table, fs=None):
+        self.model, self.img = model, img
+        self.S = int(t_table.shape[0])
+        self.nb = len(branches)
+        self.prep = model.prepare_branches(tuple(img.shape), branches, fs=fs)
+        self.ws = ops.step_workspace(img.shape[0], img.device)
+        self.counter = torch.zeros(1, dtype=torch.int32, device=img.device)
+        self.t_table = t_table.to(torch.int64).repeat(1, self.nb).contiguous().to(img.device)   # [S, B] -> [S, nb*B]
+        self.graph = None
+        self.steps_done = 0
+
+    def _reset_state(self):
+        pass
+
+    def _restart(self, img):
+        self.counter.zero_()
+        self.steps_done = 0
+        self._reset_state()
+        if img is not None:
+            self.img.copy_(img)
+        torch.cuda.synchronize()
+
+    def capture(self):
+        """Warm up once eagerly (allocates all scratch), restore the state, capture one step into a hipGraph."""
+        keep = self.img.clone()
+        self._enqueue()
+        torch.cuda.synchronize()
+        self._restart(keep)
+        self.graph = ops.DeviceGraph().capture(self._enqueue)
+        return self
+
+    def step(self):
+        # the kernels index the per-step tables, the timestep table and the pre-drawn noise by the device counter
+        if self.steps_done >= self.S:
+            raise RuntimeError(f"{type(self).__name__}: all {self.S} steps have run; rewind() first")
+        if self.graph is not None:
+            self.graph.launch()
+        else:
+            self._enqueue()
+        self.steps_done += 1
+
+    def rewind(self, x_T=None):
+        """Start over: the counter and the subclass's state to their initial values; optionally a new initial latent."""
+        self.sync()
+        self._restart(x_T)
+
+    def sync(self):
+        """Wait for the issued steps, then read the library's error word: a kernel whose bounded LDS-counter wait timed out
+        (csrc/gemm_pipe.h) has produced garbage, and that must not leave the sampler silently."""
+        if self.graph is not None:
+            self.graph.sync()
+        else:
+            torch.cuda.current_stream().synchronize()
+        _hip.check_error_word(f"{type(self).__name__}.sync")
+
+
+class FusedRun(StepRun):
+    """One fused sampling run: per step [mask blend +] batched UNet + the sampler's update kernel (`_update`: the fused
+    DDIM step here, dc_dpmpp_step in samplers/dpm_solver.py), which leaves x_prev in `img` and the step's `pred_x0`."""
 
     def __init__(self, sampler, img, branches, *, fs=None, noises=None, cfg_scale=1.0, cfg_img=None,
                  guidance_rescale=0.0, temperature=1.0, mask=None, x0=None, q_noises=None, clean_cond=False):
-        m = sampler.model
-        self.sampler, self.model = sampler, m
-        self.img = img
-        dev = img.device
-        b = img.shape[0]
-        self.S = sampler._exec_timesteps.shape[0]
-        self.nb = len(branches)
-        self.prep = m.prepare_branches(tuple(img.shape), branches, fs=fs)
-        for name, t in (("noises", noises), ("q_noises", None if (mask is None or clean_cond) else q_noises)):
-            if t is not None and t.numel() < self.S * img.numel():
-                raise ValueError(f"{name}: the step kernels read step index * {img.numel()} + i for {self.S} steps; "
-                                 f"got {t.numel()} elements")
-        self.noises = noises
-        self.pred_x0 = torch.empty_like(img)
-        self.ws = torch.empty(16 * b * 256, dtype=torch.float32, device=dev)
-        self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
         t_host = torch.as_tensor(sampler._exec_timesteps.copy(), dtype=torch.int64)
-        self.t_table = t_host[:, None].repeat(1, self.nb * b).contiguous().to(dev)          # [S, nb*B]
-        self.kw = dict(B=b, Cc=img.shape[1], THW=int(np.prod(img.shape[2:])), v_param=m.parameterization == "v",
-                       cfg_scale=cfg_scale, cfg_img=cfg_scale if cfg_img is None else cfg_img,
-                       guidance_rescale=guidance_rescale, temperature=temperature, noise_step_stride=img.numel())
-        self.graph = None
-        # mask / x0 blending ahead of every step (ddim.py:174-180): the original latent, re-noised to the step's
-        # timestep with pre-drawn q_sample noise [S, ...] unless clean_cond
-        self.blend = None
-        if mask is not None:
-            assert x0 is not None
-            full = lambda t: t.to(device=dev, dtype=torch.float32).expand_as(img).contiguous()
-            if not clean_cond and q_noises is None:
-                q_noises = torch.randn((self.S,) + tuple(img.shape), device=dev)
-            self.blend = dict(x0=full(x0), mask=full(mask), clean=bool(clean_cond),
-                              q=None if clean_cond else q_noises.to(device=dev, dtype=torch.float32).contiguous())
+        super().__init__(sampler.model, img, branches, t_host[:, None].expand(-1, img.shape[0]), fs=fs)
+        self.sampler = sampler
+        self.noises, self.blend = _step_inputs(img, self.S, noises, mask, x0, q_noises, clean_cond)
+        self.pred_x0 = torch.empty_like(img)
+        self.kw = _update_kw(self.model, img, cfg_scale, cfg_img, guidance_rescale, temperature,
+                             noise_step_stride=img.numel())
 
     def _enqueue(self):
-        """Kernel launches of one step (no allocation, no host sync): [mask blend +] batched UNet + fused DDIM update."""
         if self.blend is not None:
             b = self.blend
             ops.mask_blend(self.img, b["x0"], b["mask"], b["q"], self.sampler._tables, step_index=self.counter,
@@ -76,42 +142,8 @@ class FusedRun:
         ops.advance_counter(self.counter)
 
     def _update(self, e_c, e_u, e_i):
-        """The sampler's update kernel of one step (the fused DDIM step here; samplers/dpm_solver.py overrides it)."""
         ops.ddim_step(self.sampler._tables, e_c, e_u, e_i, self.img, self.noises, self.img, self.pred_x0, self.ws,
                       step_index=self.counter, **self.kw)
-
-    def capture(self):
-        """Warm up once eagerly (allocates all scratch), restore the state, capture one step into a hipGraph."""
-        keep = self.img.clone()
-        self._enqueue()
-        torch.cuda.synchronize()
-        self.img.copy_(keep)
-        self.counter.zero_()
-        torch.cuda.synchronize()
-        self.graph = ops.DeviceGraph().capture(self._enqueue)
-        return self
-
-    def step(self):
-        if self.graph is not None:
-            self.graph.launch()
-        else:
-            self._enqueue()
-
-    def rewind(self, x_T=None):
-        self.sync()
-        self.counter.zero_()
-        if x_T is not None:
-            self.img.copy_(x_T)
-        torch.cuda.synchronize()
-
-    def sync(self):
-        """Wait for the issued steps, then read the library's error word: a kernel whose bounded LDS-counter wait timed out
-        (csrc/gemm_pipe.h) has produced garbage, and that must not leave the sampler silently."""
-        if self.graph is not None:
-            self.graph.sync()
-        else:
-            torch.cuda.current_stream().synchronize()
-        _hip.check_error_word("FusedRun.sync")
 
 
 class DDIMSampler(object):
@@ -191,6 +223,25 @@ class DDIMSampler(object):
                 br.append(uc2)
         return br
 
+    # ------------------------------------------------------------------ what a subclass's update changes (dpm_solver.py)
+    _run_class = FusedRun
+
+    def _step_noise_plan(self, noises):
+        """(the injected step noises to use, draw one per step?, keep the draws?). The reference calls noise_like on EVERY
+        step, also when sigma_t = 0 (eta = 0): the draw is then made and discarded here too, so the generator - and with
+        a mask the q_sample noises of the later steps - stays in step with the reference for the same seed."""
+        return noises, noises is None, bool((self._tables["sigma_t"] != 0).any().item())
+
+    def _generic_update(self, img, branches, g, kwargs):
+        """The generic path's update, (img, i, noise) -> (x_prev, pred_x0), for any model exposing
+        apply_model(x, t, c, **kw) -> [B, C, ...]: p_sample_ddim on separate apply_model calls."""
+        S = self._exec_timesteps.shape[0]
+
+        def update(img, i, noise):
+            ts = torch.full((img.shape[0],), int(self._exec_timesteps[i]), device=img.device, dtype=torch.long)
+            return self.p_sample_ddim(img, branches[0], ts, index=S - i - 1, noise=noise, **g, **kwargs)
+        return update
+
     @torch.no_grad()
     def ddim_sampling(self, cond, shape, x_T=None, ddim_use_original_steps=False, callback=None, timesteps=None,
                       quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100, temperature=1.,
@@ -204,87 +255,66 @@ class DDIMSampler(object):
         m = self.model
         dev = m.device
         if dev.type != "cuda":
-            raise RuntimeError("DDIMSampler runs on the HIP path only: put the model on the GPU")
-        b = shape[0]
+            raise RuntimeError(f"{type(self).__name__} runs on the HIP path only: put the model on the GPU")
         img = (torch.randn(shape, device=dev) if x_T is None else x_T.to(dev)).to(torch.float32).contiguous().clone()
         S = self._exec_timesteps.shape[0]
         clean_cond = kwargs.pop("clean_cond", False)
-        cfg_img = kwargs.get("cfg_img")
         branches = self._branches(cond, unconditional_conditioning, unconditional_guidance_scale, kwargs)
-        nb = len(branches)
-        if cfg_img is None:
-            cfg_img = unconditional_guidance_scale
-        eta_on = bool((self._tables["sigma_t"] != 0).any().item())
         q_noises = kwargs.pop("q_noises", None)
         draw_q = mask is not None and not clean_cond and q_noises is None
-        if noises is None or draw_q:
+        noises, draw_n, keep_n = self._step_noise_plan(noises)
+        if draw_n or draw_q:
             # drawn up front so a captured graph can index them by the device step counter - in the order of the reference's
             # per-step draws: with a mask, q_sample's randn_like of step i comes before that step's noise_like
-            # (ddim.py:174-180, then p_sample_ddim :270). The reference calls noise_like on EVERY step, also when sigma_t = 0
-            # (eta = 0): the draw is then made and discarded here too, so the generator - and with a mask the q_sample noises
-            # of the later steps - stays in step with the reference for the same seed.
+            # (ddim.py:174-180, then p_sample_ddim :270)
             qs, ns = [], []
             for _ in range(S):
                 if draw_q:
                     qs.append(torch.randn(shape, device=dev))
-                if noises is None:
+                if draw_n:
                     n_i = torch.randn(shape, device=dev)
-                    if eta_on:
+                    if keep_n:
                         ns.append(n_i)
             if qs:
                 q_noises = torch.stack(qs)
             if ns:
                 noises = torch.stack(ns)
-        if noises is not None:
-            noises = noises.to(device=dev, dtype=torch.float32).contiguous()
-        if noises is not None and noises.numel() < S * img.numel():
-            raise ValueError(f"noises: {S} steps x {img.numel()} elements needed, got {noises.numel()}")
-        if mask is not None and not clean_cond and q_noises.numel() < S * img.numel():
-            raise ValueError(f"q_noises: {S} steps x {img.numel()} elements needed, got {q_noises.numel()}")
-        fast = hasattr(m, "apply_model_rows") and all(isinstance(c, dict) for c in branches)
+        g = dict(temperature=temperature, unconditional_guidance_scale=unconditional_guidance_scale, fs=fs,
+                 guidance_rescale=guidance_rescale)
         intermediates = {"x_inter": [img.clone()], "pred_x0": [img.clone()]}
-
-        if fast:
-            run = FusedRun(self, img, branches, fs=fs, noises=noises, cfg_scale=unconditional_guidance_scale,
-                           cfg_img=cfg_img, guidance_rescale=guidance_rescale, temperature=temperature, mask=mask,
-                           x0=x0, q_noises=q_noises, clean_cond=clean_cond)
+        run = None
+        if hasattr(m, "apply_model_rows") and all(isinstance(c, dict) for c in branches):
+            run = self._run_class(self, img, branches, fs=fs, noises=noises, cfg_scale=unconditional_guidance_scale,
+                                  cfg_img=kwargs.get("cfg_img"), guidance_rescale=guidance_rescale,
+                                  temperature=temperature, mask=mask, x0=x0, q_noises=q_noises, clean_cond=clean_cond)
             if use_graph:
                 run.capture()
-            for i in range(S):
+        else:
+            noises, blend = _step_inputs(img, S, noises, mask, x0, q_noises, clean_cond)
+            update = self._generic_update(img, branches, dict(g, unconditional_conditioning=unconditional_conditioning),
+                                          kwargs)
+        for i in range(S):
+            if run is not None:
                 run.step()
-                index = S - i - 1
-                log_now = index % log_every_t == 0 or index == S - 1
-                if use_graph and (callback or img_callback or log_now):
-                    run.sync()                 # the graph runs on its own stream: the step must have finished before the
-                if callback: callback(i)       # callbacks / snapshots read its results (ddim.py:196-201)
-                if img_callback: img_callback(run.pred_x0, i)
-                if log_now:
-                    intermediates["x_inter"].append(img.clone())
-                    intermediates["pred_x0"].append(run.pred_x0.clone())
+                pred_x0 = run.pred_x0
+            else:
+                if blend is not None:
+                    img = ops.mask_blend(img.contiguous().clone(), blend["x0"], blend["mask"],
+                                         None if blend["clean"] else blend["q"][i], self._tables, index=i,
+                                         clean=blend["clean"])
+                img, pred_x0 = update(img, i, None if noises is None else noises[i])
+            index = S - i - 1
+            log_now = index % log_every_t == 0 or index == S - 1
+            if run is not None and use_graph and (callback or img_callback or log_now):
+                run.sync()                     # the graph runs on its own stream: the step must have finished before the
+            if callback: callback(i)           # callbacks / snapshots read its results (ddim.py:196-201)
+            if img_callback: img_callback(pred_x0, i)
+            if log_now:
+                intermediates["x_inter"].append(img.clone())
+                intermediates["pred_x0"].append(pred_x0.clone())
+        if run is not None:
             run.sync()
             self._last_run = run
-            return img, intermediates
-
-        # generic path: any model exposing apply_model(x, t, c, **kw) -> [B, C, ...] (also mask / x0 blending)
-        for i, step in enumerate(self._exec_timesteps):
-            index = S - i - 1
-            ts = torch.full((b,), int(step), device=dev, dtype=torch.long)
-            if mask is not None:
-                assert x0 is not None
-                full = lambda t: t.to(device=dev, dtype=torch.float32).expand_as(img).contiguous()
-                qn = None if clean_cond else q_noises[i].to(dev, torch.float32).contiguous()
-                img = ops.mask_blend(img.contiguous().clone(), full(x0), full(mask), qn, self._tables, index=i,
-                                     clean=clean_cond)
-            img, pred_x0 = self.p_sample_ddim(img, cond, ts, index=index, temperature=temperature,
-                                              unconditional_guidance_scale=unconditional_guidance_scale,
-                                              unconditional_conditioning=unconditional_conditioning, fs=fs,
-                                              guidance_rescale=guidance_rescale,
-                                              noise=None if noises is None else noises[i], **kwargs)
-            if callback: callback(i)
-            if img_callback: img_callback(pred_x0, i)
-            if index % log_every_t == 0 or index == S - 1:
-                intermediates["x_inter"].append(img)
-                intermediates["pred_x0"].append(pred_x0)
         return img, intermediates
 
     @torch.no_grad()
@@ -308,22 +338,16 @@ class DDIMSampler(object):
             e_u = m.apply_model(x, t, unconditional_conditioning, **mk).to(torch.float32).contiguous()
             if uc2 is not None:
                 e_i = m.apply_model(x, t, uc2, **mk).to(torch.float32).contiguous()
-        if cfg_img is None:
-            cfg_img = unconditional_guidance_scale
         S = self._exec_timesteps.shape[0]
         if noise is None:
             noise = torch.randn(x.shape, device=dev)        # drawn even when sigma == 0, as the reference does
             if repeat_noise:
                 noise = noise[:1].expand_as(x)
         noise = noise.to(torch.float32).contiguous()
-        b = x.shape[0]
         x_prev, pred_x0 = torch.empty_like(x), torch.empty_like(x)
-        ws = torch.empty(16 * b * 256, dtype=torch.float32, device=dev)
-        ops.ddim_step(self._tables, e_c, e_u, e_i, x, noise, x_prev, pred_x0, ws, B=b, Cc=x.shape[1],
-                      THW=int(np.prod(x.shape[2:])), index=S - 1 - index, v_param=m.parameterization == "v",
-                      cfg_scale=unconditional_guidance_scale, cfg_img=cfg_img, guidance_rescale=guidance_rescale,
-                      temperature=temperature, e_nchw=True)
-        return x_prev, pred_x0
+        return ops.ddim_step(self._tables, e_c, e_u, e_i, x, noise, x_prev, pred_x0, ops.step_workspace(x.shape[0], dev),
+                             index=S - 1 - index, e_nchw=True,
+                             **_update_kw(m, x, unconditional_guidance_scale, cfg_img, guidance_rescale, temperature))
 
     @torch.no_grad()
     def stochastic_encode(self, x0, t, use_original_steps=False, noise=None):

@@ -26,7 +26,7 @@ import numpy as np
 import torch
 
 from .... import ops
-from .ddim import DDIMSampler, FusedRun
+from .ddim import DDIMSampler, FusedRun, _update_kw
 
 SOLVERS = ("dpmpp_2m", "dpmpp_2m_sde")
 LOWER_ORDER_FINAL_BELOW = 15
@@ -73,19 +73,17 @@ class DpmRun(FusedRun):
         ops.dpmpp_step(self.sampler._tables, e_c, e_u, e_i, self.img, self.noises, self.img, self.pred_x0, self.ws,
                        self.x0_hist, step_index=self.counter, **self.kw)
 
-    def capture(self):
-        super().capture()
-        self.x0_hist.zero_()                            # the eager warm-up step wrote slot 0
-        torch.cuda.synchronize()
-        return self
-
-    def rewind(self, x_T=None):
-        super().rewind(x_T)
-        self.x0_hist.zero_()
-        torch.cuda.synchronize()
+    def _reset_state(self):
+        self.x0_hist.zero_()                            # capture()'s eager warm-up step wrote slot 0
 
 
 class DPMSolverSampler(DDIMSampler):
+    """DDIMSampler with the DPM-Solver++ update: `sample` and `ddim_sampling` are DDIMSampler's. `eta` is accepted for
+    signature compatibility and not used: the stochastic variant is chosen by name (solver="dpmpp_2m_sde"), whose noise
+    is scaled by `temperature`. `noises=` ([S, *x.shape]) injects the per-step draws of the SDE variant; the ODE variant
+    draws none and ignores them."""
+    _run_class = DpmRun
+
     def __init__(self, model, solver="dpmpp_2m", schedule="linear", **kwargs):
         if solver not in SOLVERS:
             raise ValueError(f"solver must be one of {SOLVERS}, got {solver!r}")
@@ -110,127 +108,25 @@ class DPMSolverSampler(DDIMSampler):
                 self._tables["dpm_" + k] = torch.as_tensor(co[k]).float().contiguous().to(self.model.device)
         self.dpm_coefficients = co
 
-    @torch.no_grad()
-    def sample(self, S, batch_size, shape, conditioning=None, callback=None, normals_sequence=None, img_callback=None,
-               quantize_x0=False, eta=0., mask=None, x0=None, temperature=1., noise_dropout=0., score_corrector=None,
-               corrector_kwargs=None, verbose=True, schedule_verbose=False, x_T=None, log_every_t=100,
-               unconditional_guidance_scale=1., unconditional_conditioning=None, precision=None, fs=None,
-               timestep_spacing="uniform", guidance_rescale=0.0, **kwargs):
-        """DDIMSampler.sample with the DPM-Solver++ update. `eta` is accepted for signature compatibility and not
-        used: the stochastic variant is chosen by name (solver="dpmpp_2m_sde"), whose noise is scaled by
-        `temperature`. `noises=` ([S, *x.shape]) injects the per-step draws of the SDE variant; the ODE variant draws
-        none."""
-        return super().sample(S, batch_size, shape, conditioning=conditioning, callback=callback,
-                              normals_sequence=normals_sequence, img_callback=img_callback, quantize_x0=quantize_x0,
-                              eta=eta, mask=mask, x0=x0, temperature=temperature, noise_dropout=noise_dropout,
-                              score_corrector=score_corrector, corrector_kwargs=corrector_kwargs, verbose=verbose,
-                              schedule_verbose=schedule_verbose, x_T=x_T, log_every_t=log_every_t,
-                              unconditional_guidance_scale=unconditional_guidance_scale,
-                              unconditional_conditioning=unconditional_conditioning, precision=precision, fs=fs,
-                              timestep_spacing=timestep_spacing, guidance_rescale=guidance_rescale, **kwargs)
+    def _step_noise_plan(self, noises):
+        sde = "dpm_N" in self._tables                   # only the SDE variant draws (and keeps) a step noise
+        return (noises if sde else None), sde and noises is None, True
 
-    def ddim_sampling(self, *args, **kwargs):
-        # DDIMSampler.sample dispatches here
-        return self.dpm_sampling(*args, **kwargs)
-
-    @torch.no_grad()
-    def dpm_sampling(self, cond, shape, x_T=None, ddim_use_original_steps=False, callback=None, timesteps=None,
-                     quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100, temperature=1.,
-                     noise_dropout=0., score_corrector=None, corrector_kwargs=None, unconditional_guidance_scale=1.,
-                     unconditional_conditioning=None, verbose=True, precision=None, fs=None, guidance_rescale=0.0,
-                     noises=None, use_graph=False, **kwargs):
-        if ddim_use_original_steps or timesteps is not None or quantize_denoised or score_corrector is not None \
-                or noise_dropout > 0.:
-            raise NotImplementedError("only the options DynamiCrafter inference uses are implemented "
-                                      "(no original-steps / partial / quantised / corrected sampling)")
-        m = self.model
-        dev = m.device
-        if dev.type != "cuda":
-            raise RuntimeError("DPMSolverSampler runs on the HIP path only: put the model on the GPU")
-        b = shape[0]
-        img = (torch.randn(shape, device=dev) if x_T is None else x_T.to(dev)).to(torch.float32).contiguous().clone()
-        S = self._exec_timesteps.shape[0]
-        clean_cond = kwargs.pop("clean_cond", False)
-        cfg_img = kwargs.get("cfg_img")
-        branches = self._branches(cond, unconditional_conditioning, unconditional_guidance_scale, kwargs)
-        if cfg_img is None:
-            cfg_img = unconditional_guidance_scale
-        sde = "dpm_N" in self._tables
-        q_noises = kwargs.pop("q_noises", None)
-        draw_q = mask is not None and not clean_cond and q_noises is None
-        if (sde and noises is None) or draw_q:
-            # drawn up front (a captured graph indexes them by the device step counter); per step the q_sample draw
-            # comes first, as in DDIMSampler. Only the SDE variant draws step noise.
-            qs, ns = [], []
-            for _ in range(S):
-                if draw_q:
-                    qs.append(torch.randn(shape, device=dev))
-                if sde and noises is None:
-                    ns.append(torch.randn(shape, device=dev))
-            if qs:
-                q_noises = torch.stack(qs)
-            if ns:
-                noises = torch.stack(ns)
-        if not sde:
-            noises = None
-        if noises is not None:
-            noises = noises.to(device=dev, dtype=torch.float32).contiguous()
-            if noises.numel() < S * img.numel():
-                raise ValueError(f"noises: {S} steps x {img.numel()} elements needed, got {noises.numel()}")
-        if mask is not None and not clean_cond and q_noises.numel() < S * img.numel():
-            raise ValueError(f"q_noises: {S} steps x {img.numel()} elements needed, got {q_noises.numel()}")
-        fast = hasattr(m, "apply_model_rows") and all(isinstance(c, dict) for c in branches)
-        intermediates = {"x_inter": [img.clone()], "pred_x0": [img.clone()]}
-
-        if fast:
-            run = DpmRun(self, img, branches, fs=fs, noises=noises, cfg_scale=unconditional_guidance_scale,
-                         cfg_img=cfg_img, guidance_rescale=guidance_rescale, temperature=temperature, mask=mask, x0=x0,
-                         q_noises=q_noises, clean_cond=clean_cond)
-            if use_graph:
-                run.capture()
-            for i in range(S):
-                run.step()
-                index = S - i - 1
-                log_now = index % log_every_t == 0 or index == S - 1
-                if use_graph and (callback or img_callback or log_now):
-                    run.sync()
-                if callback: callback(i)
-                if img_callback: img_callback(run.pred_x0, i)
-                if log_now:
-                    intermediates["x_inter"].append(img.clone())
-                    intermediates["pred_x0"].append(run.pred_x0.clone())
-            run.sync()
-            self._last_run = run
-            return img, intermediates
-
-        # generic path: any model exposing apply_model(x, t, c, **kw) -> [B, C, ...]; the same kernel on NCTHW outputs
-        uc2 = kwargs.get("unconditional_conditioning_img_nonetext")
+    def _generic_update(self, img, branches, g, kwargs):
+        """The same kernel on the NCTHW outputs of separate apply_model calls, with a ring of its own."""
+        m, dev = self.model, img.device
         hist = torch.zeros((2,) + tuple(img.shape), dtype=torch.float32, device=dev)
-        ws = torch.empty(16 * b * 256, dtype=torch.float32, device=dev)
-        full = lambda t: t.to(device=dev, dtype=torch.float32).expand_as(img).contiguous()
-        kw = dict(B=b, Cc=img.shape[1], THW=int(np.prod(img.shape[2:])), v_param=m.parameterization == "v",
-                  cfg_scale=unconditional_guidance_scale, cfg_img=cfg_img, guidance_rescale=guidance_rescale,
-                  temperature=temperature, e_nchw=True)
-        for i, step in enumerate(self._exec_timesteps):
-            index = S - i - 1
-            ts = torch.full((b,), int(step), device=dev, dtype=torch.long)
-            if mask is not None:
-                assert x0 is not None
-                qn = None if clean_cond else q_noises[i].to(dev, torch.float32).contiguous()
-                img = ops.mask_blend(img.contiguous().clone(), full(x0), full(mask), qn, self._tables, index=i,
-                                     clean=clean_cond)
-            e = [m.apply_model(img, ts, c, fs=fs).to(torch.float32).contiguous() for c in branches]
+        ws = ops.step_workspace(img.shape[0], dev)
+        kw = _update_kw(m, img, g["unconditional_guidance_scale"], kwargs.get("cfg_img"), g["guidance_rescale"],
+                        g["temperature"], e_nchw=True)
+
+        def update(img, i, noise):
+            ts = torch.full((img.shape[0],), int(self._exec_timesteps[i]), device=dev, dtype=torch.long)
+            e = [m.apply_model(img, ts, c, fs=g["fs"]).to(torch.float32).contiguous() for c in branches]
             e += [None] * (3 - len(e))
-            x_prev, pred_x0 = torch.empty_like(img), torch.empty_like(img)
-            ops.dpmpp_step(self._tables, e[0], e[1], e[2], img, None if noises is None else noises[i], x_prev, pred_x0,
-                           ws, hist, index=i, **kw)
-            img = x_prev
-            if callback: callback(i)
-            if img_callback: img_callback(pred_x0, i)
-            if index % log_every_t == 0 or index == S - 1:
-                intermediates["x_inter"].append(img)
-                intermediates["pred_x0"].append(pred_x0)
-        return img, intermediates
+            return ops.dpmpp_step(self._tables, e[0], e[1], e[2], img, noise, torch.empty_like(img),
+                                  torch.empty_like(img), ws, hist, index=i, **kw)
+        return update
 
     def p_sample_ddim(self, *args, **kwargs):
         raise NotImplementedError("p_sample_ddim is DDIMSampler's single-step update; DPMSolverSampler is multistep")

@@ -30,7 +30,7 @@ import torch
 
 from .... import ops
 from ..utils_diffusion import make_ddim_timesteps
-from .ddim import FusedRun
+from .ddim import StepRun
 
 GRID_STEPS = 50                                  # _sample_timestep draws on the 50-step DDIM grid
 WEIGHT_TYPES = ops.SDS_WEIGHT_TYPES
@@ -88,20 +88,14 @@ def adam_tables(steps, lr, betas):
     return torch.tensor(step_size, dtype=torch.float64).float(), torch.tensor(bc2_sqrt, dtype=torch.float64).float()
 
 
-class SdsRun(FusedRun):
+class SdsRun(StepRun):
     """State of one SDS run: the latent (optimised in place), the noised latent x_t the UNet reads, Adam's moments,
     the per-step loss, the device tables / counter and optionally the captured hipGraph of a step."""
 
     def __init__(self, model, latent, branches, tables, t_table, noises, *, fs=None, cfg_scale=7.5,
                  guidance_rescale=0.0, weight_type="t", x0_formula="reference", betas=(0.9, 0.999), eps=1e-8,
                  decay=1.0):
-        self.model = model
-        self.img = latent
-        dev = latent.device
-        b = latent.shape[0]
-        self.S = int(t_table.shape[0])
-        self.nb = len(branches)
-        self.prep = model.prepare_branches(tuple(latent.shape), branches, fs=fs)
+        super().__init__(model, latent, branches, t_table, fs=fs)
         if noises.numel() < self.S * latent.numel():
             raise ValueError(f"noises: {self.S} steps x {latent.numel()} elements needed, got {noises.numel()}")
         self.noises = noises
@@ -109,15 +103,10 @@ class SdsRun(FusedRun):
         self.x_t = torch.empty_like(latent)
         self.m = torch.zeros_like(latent)
         self.v = torch.zeros_like(latent)
-        self.loss = torch.zeros(self.S, dtype=torch.float32, device=dev)
-        self.ws = torch.empty(16 * b * 256, dtype=torch.float32, device=dev)
-        self.counter = torch.zeros(1, dtype=torch.int32, device=dev)
-        self.t_table = t_table.to(torch.int64).repeat(1, self.nb).contiguous().to(dev)       # [S, nb*B]
-        self.kw = dict(B=b, Cc=latent.shape[1], THW=int(np.prod(latent.shape[2:])), weight_type=weight_type,
-                       x0_formula=x0_formula, cfg_scale=cfg_scale, guidance_rescale=guidance_rescale, betas=betas,
-                       eps=eps, decay=decay)
-        self.graph = None
-        self.steps_done = 0
+        self.loss = torch.zeros(self.S, dtype=torch.float32, device=latent.device)
+        self.kw = dict(B=latent.shape[0], Cc=latent.shape[1], THW=int(np.prod(latent.shape[2:])),
+                       weight_type=weight_type, x0_formula=x0_formula, cfg_scale=cfg_scale,
+                       guidance_rescale=guidance_rescale, betas=betas, eps=eps, decay=decay)
 
     def _enqueue(self):
         """Kernel launches of one step (no allocation, no host sync): noising, batched UNet, SDS + Adam update."""
@@ -132,36 +121,9 @@ class SdsRun(FusedRun):
         ops.advance_counter(self.counter)
 
     def _reset_state(self):
-        self.counter.zero_()
         self.m.zero_()
         self.v.zero_()
         self.loss.zero_()
-        self.steps_done = 0
-
-    def capture(self):
-        """Warm up once eagerly (allocates all scratch), restore the state, capture one step into a hipGraph."""
-        keep = self.img.clone()
-        self._enqueue()
-        torch.cuda.synchronize()
-        self.img.copy_(keep)
-        self._reset_state()
-        torch.cuda.synchronize()
-        self.graph = ops.DeviceGraph().capture(self._enqueue)
-        return self
-
-    def step(self):
-        if self.steps_done >= self.S:                # the kernels index the step tables by the counter
-            raise RuntimeError(f"SdsRun: all {self.S} steps have run; rewind() first")
-        super().step()
-        self.steps_done += 1
-
-    def rewind(self, latents=None):
-        """Start over: counter, moments and losses to zero; optionally a new initial latent."""
-        self.sync()
-        self._reset_state()
-        if latents is not None:
-            self.img.copy_(latents)
-        torch.cuda.synchronize()
 
 
 class SDSGuidance:

@@ -694,21 +694,60 @@ def vae_sample(moments, noise, z, *, N, zc, HW, scale):
     return z
 
 
-def ddim_step(tables, e_cond, e_uncond, e_img, x, noise, x_prev, pred_x0, workspace, *, B, Cc, THW, index=0,
-              step_index=None, v_param=False, cfg_scale=1.0, cfg_img=1.0, guidance_rescale=0.0, temperature=1.0,
-              e_nchw=False, ld_e=None, noise_step_stride=0):
-    """tables: dict of fp32 device vectors (a_t, a_prev, sigma_t, sqrt_one_minus_at[, sqrt_acp_t, sqrt_1macp_t,
-    scale_ratio]) indexed by the DDIM index."""
-    p = DcDdimParams()
-    for k in ("a_t", "a_prev", "sigma_t", "sqrt_one_minus_at", "sqrt_acp_t", "sqrt_1macp_t", "scale_ratio"):
+STEP_WS_FLOATS = 16 * 256     # per clip: what dc_ddim_step / dc_dpmpp_step / dc_sds_step carve their partial sums out of
+                              # (include/dcrafter_hip.h documents it, csrc/elementwise.hip static_asserts its largest layout)
+
+
+def step_workspace(B, device):
+    """The `workspace` operand of ddim_step / dpmpp_step / sds_step for B clips (scratch, no initialisation)."""
+    return torch.empty(STEP_WS_FLOATS * B, dtype=torch.float32, device=device)
+
+
+def _step_params(p, tables, fields, e_cond, index, step_index, v_param, cfg_scale, cfg_img, guidance_rescale,
+                 temperature, e_nchw, ld_e, noise_step_stride):
+    """Fill what DcDdimParams and DcDpmParams have in common (fields: struct field -> key of `tables`); returns ld_e."""
+    for f, k in fields.items():
         t = tables.get(k)
-        setattr(p, k, 0 if t is None else t.data_ptr())
+        setattr(p, f, 0 if t is None else t.data_ptr())
     p.step_index = 0 if step_index is None else step_index.data_ptr()
     p.index, p.v_param = index, 1 if v_param else 0
     p.cfg_scale, p.cfg_img, p.guidance_rescale, p.temperature = cfg_scale, cfg_img, guidance_rescale, temperature
     p.e_nchw, p.noise_step_stride = 1 if e_nchw else 0, noise_step_stride
     if ld_e is None:
         ld_e = 0 if e_nchw else e_cond.stride(0)
+    return ld_e
+
+
+def _need_step(latents, workspace, e_rows, *, B, Cc, THW, e_nchw, ld_e, noise=None, steps=1, noise_step_stride=0):
+    """Extent checks of a step launch: `latents` ((tensor, name) pairs of B*Cc*THW elements), the workspace, the e_*
+    operands in their layout and the noise of the `steps` addressable steps."""
+    n = B * Cc * THW
+    for t, nm in latents:
+        _need(t, n, nm)
+    _need(workspace, STEP_WS_FLOATS * B, "workspace")
+    for t, nm in e_rows:
+        _need(t, n if e_nchw else (B * THW - 1) * ld_e + Cc, nm)
+    _need(noise, (steps - 1) * noise_step_stride + n, "noise")
+
+
+_DDIM_FIELDS = {k: k for k in ("a_t", "a_prev", "sigma_t", "sqrt_one_minus_at", "sqrt_acp_t", "sqrt_1macp_t", "scale_ratio")}
+_DPM_FIELDS = {**{k: "dpm_" + k for k in ("A", "alpha_t", "alpha_p_r", "k", "N")},
+               **{k: k for k in ("sqrt_one_minus_at", "sqrt_acp_t", "sqrt_1macp_t", "scale_ratio")}}
+
+
+def ddim_step(tables, e_cond, e_uncond, e_img, x, noise, x_prev, pred_x0, workspace, *, B, Cc, THW, index=0,
+              step_index=None, v_param=False, cfg_scale=1.0, cfg_img=1.0, guidance_rescale=0.0, temperature=1.0,
+              e_nchw=False, ld_e=None, noise_step_stride=0):
+    """tables: dict of fp32 device vectors (a_t, a_prev, sigma_t, sqrt_one_minus_at[, sqrt_acp_t, sqrt_1macp_t,
+    scale_ratio]) indexed by the DDIM index."""
+    p = DcDdimParams()
+    ld_e = _step_params(p, tables, _DDIM_FIELDS, e_cond, index, step_index, v_param, cfg_scale, cfg_img,
+                        guidance_rescale, temperature, e_nchw, ld_e, noise_step_stride)
+    # with a device step counter the kernel reads noise[step * noise_step_stride + i], step < the number of table rows
+    _need_step(((x, "x"), (x_prev, "x_prev"), (pred_x0, "pred_x0")), workspace,
+               ((e_cond, "e_cond"), (e_uncond, "e_uncond"), (e_img, "e_img")), B=B, Cc=Cc, THW=THW, e_nchw=e_nchw,
+               ld_e=ld_e, noise=noise, steps=1 if step_index is None else int(tables["a_t"].numel()),
+               noise_step_stride=noise_step_stride)
     check(_hip.lib().dc_ddim_step(C.byref(p), _ptr(e_cond), _ptr(e_uncond), _ptr(e_img), ld_e, _ptr(x),
                                   _ptr(noise), _ptr(x_prev), _ptr(pred_x0), B, Cc, THW, _ptr(workspace),
                                   stream_ptr()), "dc_ddim_step")
@@ -721,28 +760,15 @@ def dpmpp_step(tables, e_cond, e_uncond, e_img, x, noise, x_prev, pred_x0, works
     """One DPM-Solver++ (2M / 2M SDE) update (dc_dpmpp_step). tables: dict of fp32 device vectors in execution order -
     the solver's dpm_A, dpm_alpha_t, dpm_alpha_p_r, dpm_k [, dpm_N] and the DDIM sampler's sqrt_one_minus_at /
     sqrt_acp_t / sqrt_1macp_t [/ scale_ratio]. x0_hist: [2, B*C*THW] fp32 ring of raw data predictions."""
-    n = B * Cc * THW
-    for t, nm in ((x, "x"), (x_prev, "x_prev"), (pred_x0, "pred_x0")):
-        _need(t, n, nm)
-    _need(x0_hist, 2 * n, "x0_hist")
-    _need(workspace, 16 * B * 256, "workspace")
-    if tables.get("dpm_N") is not None:
-        steps = int(tables["dpm_N"].numel()) if step_index is not None else 1
-        _need(noise, (steps - 1) * noise_step_stride + n if step_index is not None else n, "noise")
     p = _hip.DcDpmParams()
-    for k in ("A", "alpha_t", "alpha_p_r", "k", "N"):
-        t = tables.get("dpm_" + k)
-        setattr(p, k, 0 if t is None else t.data_ptr())
-    for k in ("sqrt_one_minus_at", "sqrt_acp_t", "sqrt_1macp_t", "scale_ratio"):
-        t = tables.get(k)
-        setattr(p, k, 0 if t is None else t.data_ptr())
-    p.step_index = 0 if step_index is None else step_index.data_ptr()
-    p.index, p.v_param = index, 1 if v_param else 0
-    p.cfg_scale, p.cfg_img, p.guidance_rescale, p.temperature = cfg_scale, cfg_img, guidance_rescale, temperature
-    p.e_nchw, p.noise_step_stride = 1 if e_nchw else 0, noise_step_stride
+    ld_e = _step_params(p, tables, _DPM_FIELDS, e_cond, index, step_index, v_param, cfg_scale, cfg_img,
+                        guidance_rescale, temperature, e_nchw, ld_e, noise_step_stride)
     p.x0_hist = x0_hist.data_ptr()
-    if ld_e is None:
-        ld_e = 0 if e_nchw else e_cond.stride(0)
+    _need(x0_hist, 2 * B * Cc * THW, "x0_hist")
+    _need_step(((x, "x"), (x_prev, "x_prev"), (pred_x0, "pred_x0")), workspace,
+               ((e_cond, "e_cond"), (e_uncond, "e_uncond"), (e_img, "e_img")), B=B, Cc=Cc, THW=THW, e_nchw=e_nchw,
+               ld_e=ld_e, noise=noise, steps=1 if step_index is None else int(tables["dpm_A"].numel()),
+               noise_step_stride=noise_step_stride)
     check(_hip.lib().dc_dpmpp_step(C.byref(p), _ptr(e_cond), _ptr(e_uncond), _ptr(e_img), ld_e, _ptr(x), _ptr(noise),
                                    _ptr(x_prev), _ptr(pred_x0), B, Cc, THW, _ptr(workspace), stream_ptr()),
           "dc_dpmpp_step")
@@ -804,13 +830,10 @@ def sds_step(tables, e_cond, e_uncond, x_t, latent, m, v, workspace, loss=None, 
     and step_size, bc2_sqrt [S] (samplers/sds.py); m, v: the moments; loss: [S] fp32 or None. grad_scale defaults to
     1 / (B * numel(latent)), the gradient of 0.5 mse / B."""
     n = B * Cc * THW
-    for t, nm in ((x_t, "x_t"), (latent, "latent"), (m, "m"), (v, "v")):
-        _need(t, n, nm)
-    _need(workspace, 16 * B * 256, "workspace")
     if ld_e is None:
         ld_e = 0 if e_nchw else e_cond.stride(0)
-    for t, nm in ((e_cond, "e_cond"), (e_uncond, "e_uncond")):
-        _need(t, n if e_nchw else (B * THW - 1) * ld_e + Cc, nm)
+    _need_step(((x_t, "x_t"), (latent, "latent"), (m, "m"), (v, "v")), workspace,
+               ((e_cond, "e_cond"), (e_uncond, "e_uncond")), B=B, Cc=Cc, THW=THW, e_nchw=e_nchw, ld_e=ld_e)
     if grad_scale is None:
         grad_scale = 1.0 / (B * n)
     p = _sds_params(tables, B, step_index, index, 0, weight_type, x0_formula, e_nchw, cfg_scale, guidance_rescale,

@@ -316,9 +316,44 @@ def test_rewind_equals_fresh_runs(tiny):
     second = run.img.clone()
     _, ref_b = fresh(b["x_T"])
     _, ref_a = fresh(a["x_T"])
+    with pytest.raises(RuntimeError, match="rewind"):            # step S + 1 would index past the per-step tables
+        run.step()
     assert torch.equal(first, ref_a)
     assert torch.equal(second, ref_b)
     assert not torch.equal(first, second)
+
+
+def test_default_draws_follow_the_solver(tiny):
+    """Without injected noises: dpmpp_2m (no mask) draws nothing, so the device generator is where it was; dpmpp_2m_sde
+    with a mask draws, per step, q_sample's noise and then the step's noise - the same seed gives the same sample as
+    drawing them in that order by hand and injecting them."""
+    from dynamicrafter_amd.lvdm.models.samplers.dpm_solver import DPMSolverSampler
+    model = tiny[0]
+    S = 6
+    inp = _inputs(S, seed=21)
+    mk = lambda c: {"c_crossattn": [c.to(DEV)], "c_concat": [inp["cc"].to(DEV)]}
+    x_T = inp["x_T"].to(DEV)
+    kw = dict(S=S, batch_size=1, shape=tuple(x_T.shape[1:]), conditioning=mk(inp["ctx"][0]), verbose=False,
+              unconditional_guidance_scale=7.5, unconditional_conditioning=mk(inp["ctx"][1]), x_T=x_T,
+              fs=inp["fs"].to(DEV), timestep_spacing="uniform_trailing", guidance_rescale=0.7)
+    torch.manual_seed(777)
+    out, _ = DPMSolverSampler(model, solver="dpmpp_2m").sample(**kw)
+    after = torch.randn(4, device=DEV)
+    torch.manual_seed(777)
+    assert torch.equal(after, torch.randn(4, device=DEV))
+    assert torch.isfinite(out).all()
+    mask = torch.zeros(1, 1, 4, 16, 16)
+    mask[:, :, 0] = 1.0
+    kwm = dict(kw, mask=mask.to(DEV), x0=inp["x0"].to(DEV))
+    torch.manual_seed(4321)
+    a, _ = DPMSolverSampler(model, solver="dpmpp_2m_sde").sample(**kwm)
+    torch.manual_seed(4321)
+    qs, ns = [], []
+    for _ in range(S):
+        qs.append(torch.randn(x_T.shape, device=DEV)); ns.append(torch.randn(x_T.shape, device=DEV))
+    b, _ = DPMSolverSampler(model, solver="dpmpp_2m_sde").sample(noises=torch.stack(ns), q_noises=torch.stack(qs), **kwm)
+    assert torch.isfinite(a).all()
+    assert torch.equal(a, b)
 
 
 def test_image_guided_synthesis_sampler_keyword():

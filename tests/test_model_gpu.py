@@ -510,10 +510,13 @@ def test_sampler_mask_default_noise_draw_order_and_graph_bookkeeping():
     for use_graph in (False, True):
         calls, snaps = [], []
         torch.manual_seed(99)
-        out, inter = DDIMSampler(model).sample(callback=lambda i: calls.append(i),
-                                               img_callback=lambda p, i: snaps.append((i, p.clone())), log_every_t=2,
-                                               use_graph=use_graph, **kw)
+        s = DDIMSampler(model)
+        out, inter = s.sample(callback=lambda i: calls.append(i), img_callback=lambda p, i: snaps.append((i, p.clone())),
+                              log_every_t=2, use_graph=use_graph, **kw)
         rec[use_graph] = (out, inter, calls, snaps)
+        assert (s._last_run.graph is not None) == use_graph
+        with pytest.raises(RuntimeError, match="rewind"):        # the FusedRun has run its S steps: one more would index
+            s._last_run.step()                                   # past the per-step tables
     (o0, i0, c0, s0), (o1, i1, c1, s1) = rec[False], rec[True]
     assert torch.equal(o0, o1) and c0 == c1 == list(range(S)) and len(s0) == len(s1) == S
     assert all(torch.equal(p0, p1) for (_, p0), (_, p1) in zip(s0, s1))
