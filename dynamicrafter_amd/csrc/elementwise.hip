@@ -91,6 +91,96 @@ __global__ void pack_latent_kernel(const float* __restrict__ x, const float* __r
     }
 }
 
+// Window form of pack_latent_kernel (temporal co-denoising of clips longer than the UNet's T frames: MultiDiffusion,
+// arXiv:2302.08113, along time as in Gen-L-Video, arXiv:2305.18264). x [B][Cx][T_long*HW], cc [B][Cc][T_long*HW] fp32 ->
+// rows [nrep][B][n_w][T*HW][c_pad] bf16: frame f of window w is long frame starts[step][w0 + w] + f. One thread per
+// (b, w, f, pos), the conversion of pack_latent_kernel element for element. A start outside [0, T_long - T] is clamped
+// into it (the host wrapper refuses such a table; this keeps a wrong one from reading outside x).
+__global__ void pack_latent_windows_kernel(const float* __restrict__ x, const float* __restrict__ cc,
+                                           bf16_t* __restrict__ out, const int32_t* __restrict__ starts,
+                                           const int32_t* __restrict__ step_index, int index, int S, int W, int w0, int n_w,
+                                           int B, int Cx, int Cc, int T_long, int T, int HW, int c_pad, int nrep) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+    const int THW = T * HW;
+    const int64_t total = (int64_t)B * n_w * THW;
+    if (idx >= total) return;
+    const int step = step_index ? step_index[0] : index;
+    if (step < 0 || step >= S) return;
+    const int pos = (int)(idx % THW);
+    const int bw = (int)(idx / THW);
+    const int b = bw / n_w, w = bw - b * n_w;
+    const int start = min(max(starts[(size_t)step * W + w0 + w], 0), T_long - T);
+    const size_t lpos = (size_t)start * HW + pos;              // (start + f) * HW + p
+    const size_t LTHW = (size_t)T_long * HW;
+    for (int c0 = 0; c0 < c_pad; c0 += 8) {
+        float f[8];
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const int c = c0 + e;
+            float v = 0.f;
+            if (c < Cx) v = x[((size_t)b * Cx + c) * LTHW + lpos];
+            else if (c < Cx + Cc) v = cc[((size_t)b * Cc + (c - Cx)) * LTHW + lpos];
+            f[e] = v;
+        }
+        const uint4 pk = pack_bf8(f);
+        for (int r = 0; r < nrep; ++r)
+            *reinterpret_cast<uint4*>(out + ((size_t)r * total + idx) * c_pad + c0) = pk;
+    }
+}
+
+// Blend of the UNet's window outputs back onto the long clip: e rows [(k, b, w, f, p)][ld_e] fp32 (first C channels) ->
+// out rows [(k, b, F, p)][ld_out], out = sum_w wn[step][w0 + w][F - start_w] * e[k, b, w, F - start_w, p] over the n_w windows
+// of this call that contain F with a non-zero weight, in ascending w: the first term is a product, every later one a fused
+// multiply-add, so a chunked evaluation (accumulate: start from what out holds) rounds as the unchunked one (the values are
+// equal; where a later chunk brings a frame's first term, a product of -0 arrives as +0) and a single window of weight 1
+// returns its input. One thread per output row; VEC: C == 4 with 16-byte aligned rows, one float4 load per term.
+template <bool VEC>
+__global__ __launch_bounds__(256) void window_merge_kernel(const float* __restrict__ e, int ld_e, float* __restrict__ out,
+                                                           int ld_out, const int32_t* __restrict__ starts,
+                                                           const float* __restrict__ wn,
+                                                           const int32_t* __restrict__ step_index, int index, int S, int W,
+                                                           int w0, int n_w, int KB, int C, int T_long, int T, int HW,
+                                                           int accumulate) {
+    const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;       // (kb, F, p)
+    const int64_t total = (int64_t)KB * T_long * HW;
+    if (idx >= total) return;
+    const int step = step_index ? step_index[0] : index;
+    if (step < 0 || step >= S) return;
+    const int p = (int)(idx % HW);
+    const int64_t r = idx / HW;
+    const int F = (int)(r % T_long);
+    const int kb = (int)(r / T_long);
+    const int32_t* st = starts + (size_t)step * W + w0;
+    const float* wt = wn + ((size_t)step * W + w0) * T;
+    float* o = out + (size_t)idx * ld_out;
+    constexpr int MAXC = 4;
+    for (int c0 = 0; c0 < C; c0 += MAXC) {
+        const int nc = min(MAXC, C - c0);
+        float acc[MAXC] = {0.f, 0.f, 0.f, 0.f};
+        bool have = false;
+        if (accumulate) {
+            have = true;
+            if (VEC) { const float4 v = *reinterpret_cast<const float4*>(o); acc[0] = v.x; acc[1] = v.y; acc[2] = v.z; acc[3] = v.w; }
+            else for (int c = 0; c < nc; ++c) acc[c] = o[c0 + c];
+        }
+        for (int w = 0; w < n_w; ++w) {
+            const int f = F - st[w];
+            if (f < 0 || f >= T) continue;
+            const float g = wt[(size_t)w * T + f];
+            if (g == 0.f) continue;                            // padding / duplicate window: its output is never read
+            const float* src = e + ((((size_t)kb * n_w + w) * T + f) * HW + p) * ld_e + c0;
+            float v[MAXC] = {0.f, 0.f, 0.f, 0.f};
+            if (VEC) { const float4 q = *reinterpret_cast<const float4*>(src); v[0] = q.x; v[1] = q.y; v[2] = q.z; v[3] = q.w; }
+            else for (int c = 0; c < nc; ++c) v[c] = src[c];
+#pragma unroll
+            for (int c = 0; c < MAXC; ++c) acc[c] = have ? __fmaf_rn(g, v[c], acc[c]) : __fmul_rn(g, v[c]);
+            have = true;
+        }
+        if (VEC) *reinterpret_cast<float4*>(o) = make_float4(acc[0], acc[1], acc[2], acc[3]);
+        else for (int c = 0; c < nc; ++c) o[c0 + c] = acc[c];
+    }
+}
+
 __global__ void nchw_to_rows_kernel(const float* __restrict__ x, bf16_t* __restrict__ out, int N, int C, int HW,
                                     int c_pad, float scale) {
     const int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
@@ -659,6 +749,42 @@ extern "C" int dc_pack_latent(const float* x, const float* cc, uint16_t* out, in
     const int64_t total = (int64_t)B * T * HW;
     hipLaunchKernelGGL(pack_latent_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream_, x,
                        cc, out, B, Cx, Cc, T * HW, c_pad, nrep);
+    DC_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dc_pack_latent_windows(const float* x, const float* cc, uint16_t* out, const int32_t* starts,
+                                      const int32_t* step_index, int index, int S, int W, int w0, int n_w, int B, int Cx,
+                                      int Cc, int T_long, int T, int HW, int c_pad, int nrep, void* stream_) {
+    if (!x || !out || !starts || (Cc > 0 && !cc)) return DC_ERR_ARG;
+    if (c_pad % 8 != 0 || Cx < 1 || Cc < 0 || c_pad < Cx + Cc || nrep < 1 || B < 1 || HW < 1 || T < 1 || T_long < T || S < 1 ||
+        W < 1 || w0 < 0 || n_w < 1 || w0 + n_w > W || (!step_index && (index < 0 || index >= S)))
+        return DC_ERR_SHAPE;
+    const int64_t total = (int64_t)B * n_w * T * HW;
+    if (total > INT32_MAX || (int64_t)T_long * HW > INT32_MAX) return DC_ERR_SHAPE;
+    hipLaunchKernelGGL(pack_latent_windows_kernel, dim3((unsigned)((total + 255) / 256)), dim3(256), 0, (hipStream_t)stream_,
+                       x, cc, out, starts, step_index, index, S, W, w0, n_w, B, Cx, Cc, T_long, T, HW, c_pad, nrep);
+    DC_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dc_window_merge(const float* e, int ld_e, float* out, int ld_out, const int32_t* starts, const float* wn,
+                               const int32_t* step_index, int index, int S, int W, int w0, int n_w, int nb, int B, int C,
+                               int T_long, int T, int HW, int accumulate, void* stream_) {
+    if (!e || !out || !starts || !wn) return DC_ERR_ARG;
+    if (nb < 1 || B < 1 || C < 1 || ld_e < C || ld_out < C || HW < 1 || T < 1 || T_long < T || S < 1 || W < 1 || w0 < 0 ||
+        n_w < 1 || w0 + n_w > W || (!step_index && (index < 0 || index >= S)))
+        return DC_ERR_SHAPE;
+    const int64_t total = (int64_t)nb * B * T_long * HW;
+    if (total > INT32_MAX || (int64_t)nb * B * n_w * T * HW > INT32_MAX) return DC_ERR_SHAPE;
+    const bool vec = C == 4 && ld_e % 4 == 0 && ld_out % 4 == 0 && ((uintptr_t)e % 16) == 0 && ((uintptr_t)out % 16) == 0;
+    const dim3 grid((unsigned)((total + 255) / 256));
+    if (vec)
+        hipLaunchKernelGGL(window_merge_kernel<true>, grid, dim3(256), 0, (hipStream_t)stream_, e, ld_e, out, ld_out, starts,
+                           wn, step_index, index, S, W, w0, n_w, nb * B, C, T_long, T, HW, accumulate);
+    else
+        hipLaunchKernelGGL(window_merge_kernel<false>, grid, dim3(256), 0, (hipStream_t)stream_, e, ld_e, out, ld_out, starts,
+                           wn, step_index, index, S, W, w0, n_w, nb * B, C, T_long, T, HW, accumulate);
     DC_CHECK_LAUNCH();
     return 0;
 }

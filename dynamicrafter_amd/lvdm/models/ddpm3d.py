@@ -285,13 +285,19 @@ class LatentDiffusion(DDPM):
         return out[0] if isinstance(out, tuple) else out
 
     # ------------------------------------------------------------------ MI355X fast path
-    def prepare_branches(self, x_shape, branches, fs=None):
+    def prepare_branches(self, x_shape, branches, fs=None, windows=None):
         """Step-invariant part of a guided UNet evaluation: per-frame context rows of every conditioning branch
         (cond / uncond [/ image-only]), their c_concat tensors and the fs table. Done once per sampler call,
-        outside the per-step (graph-captured) region; allocates."""
+        outside the per-step (graph-captured) region; allocates.
+        windows = dict(T=, n_w=) (apply_model_windows): x_shape is the long clip's, one UNet call takes n_w windows of
+        T frames of each of the B clips, so the context rows and the fs entry of clip b are repeated for its n_w
+        windows (frame j of every window reads image-token set j); c_concat stays T_long frames long."""
         net = self.model.diffusion_model
         key = self.model.conditioning_key
         B, Cx, T, H, W = x_shape
+        n_w = 1
+        if windows is not None:
+            T, n_w = int(windows["T"]), int(windows["n_w"])
         dev = self.device
         nb = len(branches)
         ccs, ctx_all, Lc = [], None, None
@@ -303,7 +309,9 @@ class LatentDiffusion(DDPM):
             ccs.append(cc)
             ca = cond["c_crossattn"]
             ctx = (ca[0] if len(ca) == 1 else torch.cat(ca, 1)).to(dev)
-            rows, Lc = net.build_context_rows(ctx, B, T, tag=f"ctx_b{k}")
+            if windows is not None:
+                ctx = ctx.repeat_interleave(n_w, dim=0)
+            rows, Lc = net.build_context_rows(ctx, B * n_w, T, tag=f"ctx_b{k}")
             if ctx_all is None:
                 ctx_all = net._arena.get("ctx_all", nb * rows.shape[0], rows.shape[1], device=dev)
             ops.copy2d(rows, ctx_all[k * rows.shape[0]:(k + 1) * rows.shape[0]])
@@ -311,7 +319,10 @@ class LatentDiffusion(DDPM):
         if net.fs_condition:
             if fs is None:
                 fs = torch.full((B,), net.default_fs, dtype=torch.int64, device=dev)
-            fs_table = fs.to(device=dev, dtype=torch.int64).repeat(nb).contiguous()
+            fs_table = fs.to(device=dev, dtype=torch.int64)
+            if windows is not None:
+                fs_table = fs_table.repeat_interleave(n_w)
+            fs_table = fs_table.repeat(nb).contiguous()
         # branches that share the latent AND the concat conditioning have identical activations up to the first
         # cross-attention: the UNet computes that prefix once (openaimodel3d.forward_rows shared_prefix)
         same_cc = all((c is ccs[0]) or (c is not None and ccs[0] is not None and c.shape == ccs[0].shape
@@ -321,7 +332,7 @@ class LatentDiffusion(DDPM):
         # once per sampler call, instead of in every UNet forward of every step
         ctx_kv = net.precompute_context_kv(ctx_all) if os.environ.get("DC_HOIST_CTX_KV", "1") != "0" else None
         return dict(nb=nb, ccs=ccs, ctx_all=ctx_all, Lc=Lc, fs_table=fs_table, shape=tuple(x_shape), share=share,
-                    ctx_kv=ctx_kv)
+                    ctx_kv=ctx_kv, win=None if windows is None else dict(T=T, n_w=n_w))
 
     def apply_model_rows(self, x, prep, t_table, t_index=None):
         """All branches of `prep` on the same latent x as ONE batched UNet forward (kernel launches only; safe
@@ -339,6 +350,45 @@ class LatentDiffusion(DDPM):
         return net.forward_rows(xr, t_table, prep["ctx_all"], B=nb * B, T=T, H=H, W=W, Lc=Lc, n_text=min(77, Lc),
                                 fs_table=prep["fs_table"], t_index=t_index, shared_prefix=prep.get("share", 1),
                                 ctx_kv=prep.get("ctx_kv"))
+
+    def max_windows_per_call(self, x_shape, nb, T):
+        """The most T-frame windows of a [B, C, T_long, h, w] latent one batched UNet call can take with nb branches:
+        every scratch buffer of the forward must stay under 2^31 elements (rows x row stride)."""
+        B, _, _, H, W = x_shape
+        net = self.model.diffusion_model
+        # per clip: the widest activation buffer, and the context rows (at most 77 + 16 tokens per frame) with their
+        # widest projection, which outgrow the activations on a latent of fewer than ~100 positions
+        per_clip = max(T * H * W * net.max_row_width(), T * (77 + 16) * net.max_context_row_width())
+        n = int((2 ** 31 - 1) // per_clip) // (nb * B)
+        if n < 1:
+            raise ValueError(f"one window of {nb} x {B} clips of {T} x {H} x {W} exceeds the 2^31-element scratch limit")
+        return n
+
+    def apply_model_windows(self, x, prep, t_table, plan, out, t_index=None, index=0):
+        """apply_model_rows for a long latent x fp32 [B, 4, T_long, h, w]: the UNet runs on the windows of the current
+        step of `plan` (ops.window_tables), prep["win"]["n_w"] of them per call with B_eff = nb * B * n_w, and each
+        call's output is blended into `out` before the next call reuses the arena's output buffer. t_table int64
+        [n_steps, nb * B * n_w]. Kernel launches only. Returns `out`: fp32 rows [nb * B * T_long * h * w, C], branch-major,
+        the layout dc_ddim_step / dc_dpmpp_step consume with THW = T_long * h * w."""
+        net = self.model.diffusion_model
+        B, Cx, TL, H, W = prep["shape"]
+        nb, T, n_w = prep["nb"], prep["win"]["T"], prep["win"]["n_w"]
+        if plan["W"] % n_w or plan["T"] != T or plan["T_long"] != TL:
+            raise ValueError(f"window plan (W {plan['W']}, T {plan['T']}, T_long {plan['T_long']}) does not fit calls of "
+                             f"{n_w} windows of {T} frames on {TL}")
+        Mc = B * n_w * T * H * W
+        xr = net._arena.get("x_rows", nb * Mc, C_IN_PAD, device=x.device)
+        Lc = prep["Lc"]
+        for w0 in range(0, plan["W"], n_w):
+            for k, cc in enumerate(prep["ccs"]):
+                ops.pack_latent_windows(x, cc, xr[k * Mc:(k + 1) * Mc], plan, B=B, Cx=Cx, Cc=0 if cc is None else cc.shape[1],
+                                        HW=H * W, w0=w0, n_w=n_w, index=index, step_index=t_index)
+            e = net.forward_rows(xr, t_table, prep["ctx_all"], B=nb * B * n_w, T=T, H=H, W=W, Lc=Lc, n_text=min(77, Lc),
+                                 fs_table=prep["fs_table"], t_index=t_index, shared_prefix=prep.get("share", 1),
+                                 ctx_kv=prep.get("ctx_kv"))
+            ops.window_merge(e, out, plan, nb=nb, B=B, C=net.out_channels, HW=H * W, w0=w0, n_w=n_w, index=index,
+                             step_index=t_index, accumulate=w0 > 0)
+        return out
 
 
 class LatentVisualDiffusion(LatentDiffusion):

@@ -14,19 +14,29 @@ behaves as the reference's, including the 3-branch guidance of ddim_multiplecond
   * sqrt(1 - a_prev - sigma^2) is clamped at 0 (the reference can produce NaN there: SURVEY §8 a2).
   * `mask` / `x0` blending (reference :174-180) is one more kernel ahead of the step (dc_mask_blend: q_sample + blend),
     inside the captured graph; `q_noises=` (tensor [S, *x.shape]) injects the q_sample draws (parity tests).
+  * `window_stride=` (not in the reference) samples clips longer than the UNet's `temporal_length` by temporal
+    co-denoising: `shape`'s frame count is then T_long, the UNet runs on overlapping windows of the long latent and their
+    outputs are blended ahead of the unchanged update (samplers/windows.py, WindowedRun below).
 """
 import numpy as np
 import torch
 
 from .... import _hip, ops
 from ..utils_diffusion import make_ddim_sampling_parameters, make_ddim_timesteps
+from .windows import pad_plan, window_plan, windows_per_call
 
 
-def _step_inputs(img, S, noises, mask, x0, q_noises, clean_cond):
+def _step_inputs(img, S, noises, mask, x0, q_noises, clean_cond, long_branches=None):
     """The per-step draws and the mask operands as the kernels read them, checked in this one place for the fused and
     the generic path: fp32 on the latent's device, `noises` / `q_noises` long enough for S steps, x0 / mask expanded to
-    the latent's shape. Returns (noises, blend); blend is None without a mask."""
+    the latent's shape. With windows (`long_branches`: the conditioning branches) everything is T_long frames long, the
+    c_concat entries included. Returns (noises, blend); blend is None without a mask."""
     f32 = lambda t: t.to(device=img.device, dtype=torch.float32)
+    for k, c in enumerate(long_branches or ()):
+        for cc in (c.get("c_concat") or ()) if isinstance(c, dict) else ():
+            if cc.dim() != img.dim() or cc.shape[2] != img.shape[2]:
+                raise ValueError(f"windowed sampling: c_concat of branch {k} has shape {tuple(cc.shape)}, the latent has "
+                                 f"{img.shape[2]} frames")
     # mask / x0 blending ahead of every step (ddim.py:174-180): the original latent, re-noised to the step's timestep
     # with pre-drawn q_sample noise [S, ...] unless clean_cond
     blend = None
@@ -59,14 +69,19 @@ class StepRun:
     ending in ops.advance_counter), and `_reset_state()`, which puts back whatever else a step changes besides the
     latent and the counter. `step()` advances the device counter by one; after `S` steps `rewind()` starts over."""
 
-    def __init__(self, model, img, branches, t_table, fs=None):
+    def __init__(self, model, img, branches, t_table, fs=None, windows=None):
         self.model, self.img = model, img
         self.S = int(t_table.shape[0])
         self.nb = len(branches)
-        self.prep = model.prepare_branches(tuple(img.shape), branches, fs=fs)
+        t_table = t_table.to(torch.int64)
+        if windows is None:
+            self.prep = model.prepare_branches(tuple(img.shape), branches, fs=fs)
+        else:                                           # the UNet batch is (branch, clip, window): WindowedRun
+            self.prep = model.prepare_branches(tuple(img.shape), branches, fs=fs, windows=windows)
+            t_table = t_table.repeat_interleave(int(windows["n_w"]), dim=1)
         self.ws = ops.step_workspace(img.shape[0], img.device)
         self.counter = torch.zeros(1, dtype=torch.int32, device=img.device)
-        self.t_table = t_table.to(torch.int64).repeat(1, self.nb).contiguous().to(img.device)   # [S, B] -> [S, nb*B]
+        self.t_table = t_table.repeat(1, self.nb).contiguous().to(img.device)   # [S, B] -> [S, nb*B]
         self.graph = None
         self.steps_done = 0
 
@@ -120,11 +135,13 @@ class FusedRun(StepRun):
     DDIM step here, dc_dpmpp_step in samplers/dpm_solver.py), which leaves x_prev in `img` and the step's `pred_x0`."""
 
     def __init__(self, sampler, img, branches, *, fs=None, noises=None, cfg_scale=1.0, cfg_img=None,
-                 guidance_rescale=0.0, temperature=1.0, mask=None, x0=None, q_noises=None, clean_cond=False):
+                 guidance_rescale=0.0, temperature=1.0, mask=None, x0=None, q_noises=None, clean_cond=False,
+                 windows=None):
         t_host = torch.as_tensor(sampler._exec_timesteps.copy(), dtype=torch.int64)
-        super().__init__(sampler.model, img, branches, t_host[:, None].expand(-1, img.shape[0]), fs=fs)
+        super().__init__(sampler.model, img, branches, t_host[:, None].expand(-1, img.shape[0]), fs=fs, windows=windows)
         self.sampler = sampler
-        self.noises, self.blend = _step_inputs(img, self.S, noises, mask, x0, q_noises, clean_cond)
+        self.noises, self.blend = _step_inputs(img, self.S, noises, mask, x0, q_noises, clean_cond,
+                                               long_branches=None if windows is None else branches)
         self.pred_x0 = torch.empty_like(img)
         self.kw = _update_kw(self.model, img, cfg_scale, cfg_img, guidance_rescale, temperature,
                              noise_step_stride=img.numel())
@@ -134,17 +151,96 @@ class FusedRun(StepRun):
             b = self.blend
             ops.mask_blend(self.img, b["x0"], b["mask"], b["q"], self.sampler._tables, step_index=self.counter,
                            clean=b["clean"], noise_step_stride=self.img.numel())
-        e = self.model.apply_model_rows(self.img, self.prep, self.t_table, t_index=self.counter)
+        e = self._evaluate()
         M = self.kw["B"] * self.kw["THW"]
         e_u = e[M:2 * M] if self.nb > 1 else None
         e_i = e[2 * M:3 * M] if self.nb > 2 else None
         self._update(e[:M], e_u, e_i)
         ops.advance_counter(self.counter)
 
+    def _evaluate(self):
+        """The raw model output of every branch on the latent: fp32 rows [nb * B * THW, C], branch-major."""
+        return self.model.apply_model_rows(self.img, self.prep, self.t_table, t_index=self.counter)
+
     def _update(self, e_c, e_u, e_i):
         ops.ddim_step(self.sampler._tables, e_c, e_u, e_i, self.img, self.noises, self.img, self.pred_x0, self.ws,
                       step_index=self.counter, **self.kw)
 
+
+class WindowedRun:
+    """Mixin ahead of FusedRun or a subclass of it (`windowed(cls)`): the latent is a clip of T_long > T frames and the
+    model evaluation of a step is, per chunk of `n_w` windows, window pack per branch + one batched UNet forward with
+    B_eff = nb * B * n_w + blend into the long output rows. Mask blend, the sampler's update (`_update`, unchanged, on
+    T_long * HW positions), the counter, capture / step / rewind / sync are the base run's. The window starts and blend
+    weights are two more device tables indexed by the step counter, so one captured step graph serves windows that
+    move from step to step.
+
+    window = dict(T=, stride=, weights=, shift=, per_call=): per_call caps the windows of one UNet call (None: the most
+    that keeps every scratch buffer under 2^31 elements); the plan is padded to whole calls with weight-0 windows."""
+
+    def __init__(self, sampler, img, branches, *, window, **kw):
+        model = sampler.model
+        T, nb, S = int(window["T"]), len(branches), int(sampler._exec_timesteps.shape[0])
+        plan = window.get("plan")                       # ddim_sampling has built it already (argument checks)
+        if plan is None:
+            plan = window_plan(img.shape[2], T, window["stride"], window.get("weights", "triangle"),
+                               window.get("shift", 0), S)
+        W = plan[0].shape[1]
+        n_w = windows_per_call(W, model.max_windows_per_call(tuple(img.shape), nb, T), window.get("per_call"))
+        starts, wn = pad_plan(*plan, n_w)
+        super().__init__(sampler, img, branches, windows=dict(T=T, n_w=n_w), **kw)
+        self.plan = ops.window_tables(starts, wn, T_long=img.shape[2], T=T, device=img.device)
+        rows = nb * img.shape[0] * int(np.prod(img.shape[2:]))
+        self.e_long = torch.empty((rows, model.model.diffusion_model.out_channels), dtype=torch.float32, device=img.device)
+
+    def _evaluate(self):
+        return self.model.apply_model_windows(self.img, self.prep, self.t_table, self.plan, self.e_long,
+                                              t_index=self.counter)
+
+
+_windowed_classes = {}
+
+
+def windowed(run_class):
+    """The windowed form of a FusedRun class (FusedRun itself, DpmRun): WindowedRun mixed in ahead of it."""
+    if run_class not in _windowed_classes:
+        _windowed_classes[run_class] = type("Windowed" + run_class.__name__, (WindowedRun, run_class), {})
+    return _windowed_classes[run_class]
+
+
+class _WindowedModel:
+    """The generic path's windows: a stand-in for the model whose apply_model evaluates the wrapped model on every
+    window of the current step (`step`, set by the sampling loop) and blends the outputs with the same plan tables,
+    in plain torch indexing on the device. Every other attribute is the wrapped model's."""
+
+    def __init__(self, model, starts, wn, T, device):
+        self._m, self._starts, self._T = model, starts, T
+        self._wn = torch.from_numpy(wn).to(device)
+        self.step = 0
+
+    def __getattr__(self, name):
+        return getattr(self._m, name)
+
+    def apply_model(self, x, t, c, **kw):
+        T, out = self._T, None
+        for w, s in enumerate(int(v) for v in self._starts[self.step]):
+            g = self._wn[self.step, w]
+            if not bool((g != 0).any()):
+                continue                                # padding / duplicate window
+            cw = c
+            if isinstance(c, dict) and c.get("c_concat") is not None:
+                cw = dict(c, c_concat=[cc[:, :, s:s + T].contiguous() for cc in c["c_concat"]])
+            e = self._m.apply_model(x[:, :, s:s + T].contiguous(), t, cw, **kw).to(torch.float32)
+            if out is None:
+                out = torch.zeros(x.shape[:1] + e.shape[1:2] + x.shape[2:], dtype=torch.float32, device=x.device)
+            # dc_window_merge's order and roundings, in ascending w: the product of two fp32 numbers is exact in float64;
+            # the sum is then rounded to float64 and to fp32. That is a fused multiply-add except where the float64 sum
+            # lands within 2^-29 ulp of a midpoint between two fp32 numbers (double rounding, about one term in 10^8), so the
+            # two paths agree bitwise on almost every element, not by construction on all: with other inputs or another
+            # toolchain a last-bit difference can appear
+            seg = out[:, :, s:s + T]
+            seg.copy_((seg.double() + g.double().view(1, 1, T, 1, 1) * e.double()).float())
+        return out
 
 class DDIMSampler(object):
     def __init__(self, model, schedule="linear", **kwargs):
@@ -232,14 +328,15 @@ class DDIMSampler(object):
         a mask the q_sample noises of the later steps - stays in step with the reference for the same seed."""
         return noises, noises is None, bool((self._tables["sigma_t"] != 0).any().item())
 
-    def _generic_update(self, img, branches, g, kwargs):
+    def _generic_update(self, img, branches, g, kwargs, model=None):
         """The generic path's update, (img, i, noise) -> (x_prev, pred_x0), for any model exposing
-        apply_model(x, t, c, **kw) -> [B, C, ...]: p_sample_ddim on separate apply_model calls."""
+        apply_model(x, t, c, **kw) -> [B, C, ...]: p_sample_ddim on separate apply_model calls. `model`: what to
+        evaluate instead of self.model (the windowed stand-in)."""
         S = self._exec_timesteps.shape[0]
 
         def update(img, i, noise):
             ts = torch.full((img.shape[0],), int(self._exec_timesteps[i]), device=img.device, dtype=torch.long)
-            return self.p_sample_ddim(img, branches[0], ts, index=S - i - 1, noise=noise, **g, **kwargs)
+            return self.p_sample_ddim(img, branches[0], ts, index=S - i - 1, noise=noise, model=model, **g, **kwargs)
         return update
 
     @torch.no_grad()
@@ -247,7 +344,8 @@ class DDIMSampler(object):
                       quantize_denoised=False, mask=None, x0=None, img_callback=None, log_every_t=100, temperature=1.,
                       noise_dropout=0., score_corrector=None, corrector_kwargs=None, unconditional_guidance_scale=1.,
                       unconditional_conditioning=None, verbose=True, precision=None, fs=None, guidance_rescale=0.0,
-                      noises=None, use_graph=False, **kwargs):
+                      noises=None, use_graph=False, window_stride=None, window_weights="triangle", window_shift=0,
+                      windows_per_call=None, **kwargs):
         if ddim_use_original_steps or timesteps is not None or quantize_denoised or score_corrector is not None \
                 or noise_dropout > 0.:
             raise NotImplementedError("only the options DynamiCrafter inference uses are implemented "
@@ -258,6 +356,15 @@ class DDIMSampler(object):
             raise RuntimeError(f"{type(self).__name__} runs on the HIP path only: put the model on the GPU")
         img = (torch.randn(shape, device=dev) if x_T is None else x_T.to(dev)).to(torch.float32).contiguous().clone()
         S = self._exec_timesteps.shape[0]
+        window = None
+        if window_stride is not None:
+            T = getattr(m, "temporal_length", None)
+            if T is None:
+                raise ValueError("windowed sampling needs the model's temporal_length (the frames one UNet call takes)")
+            # the one host plan of the call: refuses bad values here, then serves the fused run or the generic stand-in
+            plan_host = window_plan(img.shape[2], T, window_stride, window_weights, window_shift, S)
+            window = dict(T=int(T), stride=window_stride, weights=window_weights, shift=window_shift,
+                          per_call=windows_per_call, plan=plan_host)
         clean_cond = kwargs.pop("clean_cond", False)
         branches = self._branches(cond, unconditional_conditioning, unconditional_guidance_scale, kwargs)
         q_noises = kwargs.pop("q_noises", None)
@@ -284,15 +391,22 @@ class DDIMSampler(object):
         intermediates = {"x_inter": [img.clone()], "pred_x0": [img.clone()]}
         run = None
         if hasattr(m, "apply_model_rows") and all(isinstance(c, dict) for c in branches):
-            run = self._run_class(self, img, branches, fs=fs, noises=noises, cfg_scale=unconditional_guidance_scale,
-                                  cfg_img=kwargs.get("cfg_img"), guidance_rescale=guidance_rescale,
-                                  temperature=temperature, mask=mask, x0=x0, q_noises=q_noises, clean_cond=clean_cond)
+            cls, wkw = (self._run_class, {}) if window is None else (windowed(self._run_class), dict(window=window))
+            run = cls(self, img, branches, fs=fs, noises=noises, cfg_scale=unconditional_guidance_scale,
+                      cfg_img=kwargs.get("cfg_img"), guidance_rescale=guidance_rescale, temperature=temperature,
+                      mask=mask, x0=x0, q_noises=q_noises, clean_cond=clean_cond, **wkw)
             if use_graph:
                 run.capture()
         else:
-            noises, blend = _step_inputs(img, S, noises, mask, x0, q_noises, clean_cond)
+            noises, blend = _step_inputs(img, S, noises, mask, x0, q_noises, clean_cond,
+                                         long_branches=None if window is None else branches)
+        proxy = None
+        if run is None:
+            if window is not None:
+                # the update's apply_model calls go to a stand-in that evaluates the model per window and blends
+                proxy = _WindowedModel(m, *plan_host, window["T"], dev)
             update = self._generic_update(img, branches, dict(g, unconditional_conditioning=unconditional_conditioning),
-                                          kwargs)
+                                          kwargs, **({} if proxy is None else {"model": proxy}))
         for i in range(S):
             if run is not None:
                 run.step()
@@ -302,6 +416,8 @@ class DDIMSampler(object):
                     img = ops.mask_blend(img.contiguous().clone(), blend["x0"], blend["mask"],
                                          None if blend["clean"] else blend["q"][i], self._tables, index=i,
                                          clean=blend["clean"])
+                if proxy is not None:
+                    proxy.step = i
                 img, pred_x0 = update(img, i, None if noises is None else noises[i])
             index = S - i - 1
             log_now = index % log_every_t == 0 or index == S - 1
@@ -322,11 +438,11 @@ class DDIMSampler(object):
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
                       unconditional_guidance_scale=1., unconditional_conditioning=None, uc_type=None,
                       conditional_guidance_scale_temporal=None, mask=None, x0=None, guidance_rescale=0.0, noise=None,
-                      cfg_img=None, **kwargs):
+                      cfg_img=None, model=None, **kwargs):
         """One DDIM update from separate apply_model calls (reference :205-279 / multiplecond :211-285)."""
         if use_original_steps or quantize_denoised or score_corrector is not None or noise_dropout > 0.:
             raise NotImplementedError
-        m = self.model
+        m = self.model if model is None else model
         dev = x.device
         x = x.to(torch.float32).contiguous()
         uc2 = kwargs.pop("unconditional_conditioning_img_nonetext", None)

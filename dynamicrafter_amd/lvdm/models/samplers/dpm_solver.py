@@ -112,9 +112,9 @@ class DPMSolverSampler(DDIMSampler):
         sde = "dpm_N" in self._tables                   # only the SDE variant draws (and keeps) a step noise
         return (noises if sde else None), sde and noises is None, True
 
-    def _generic_update(self, img, branches, g, kwargs):
+    def _generic_update(self, img, branches, g, kwargs, model=None):
         """The same kernel on the NCTHW outputs of separate apply_model calls, with a ring of its own."""
-        m, dev = self.model, img.device
+        m, dev = self.model if model is None else model, img.device
         hist = torch.zeros((2,) + tuple(img.shape), dtype=torch.float32, device=dev)
         ws = ops.step_workspace(img.shape[0], dev)
         kw = _update_kw(m, img, g["unconditional_guidance_scale"], kwargs.get("cfg_img"), g["guidance_rescale"],

@@ -689,6 +689,31 @@ class UNetModel(nn.Module):
         conv = dict(IH=g["H"], IW=g["W"], OH=g["H"], OW=g["W"], stride=1, pad=1, ups=0)
         return ops.gemm(n, Wt["out_conv"], y, conv=conv)
 
+    def max_row_width(self):
+        """The widest scratch row of forward_rows, in elements per row of the input resolution: per block the widest
+        buffer it touches (a ResBlock's input - the [h | skip] concat on the way up - and output, a transformer's GEGLU
+        hidden of 4 ch beside its 3 ch qkv), divided by the 4^level fewer rows it has; at least the 128-wide im2col of
+        conv_in. What bounds the clips one call may take (every buffer's rows x stride < 2^31)."""
+        down_path, middle, up_path = self._layout
+        best, ds = 128.0, 1
+        for blk in list(down_path) + [middle] + list(up_path):
+            for kind, a in blk:
+                if kind == "down":
+                    ds *= 2
+                wide = {"res": lambda: max(a["cin"], a["cout"]), "spatial": lambda: 4 * a["ch"],
+                        "temporal": lambda: 4 * a["ch"]}.get(kind, lambda: a.get("cout", a.get("ch", 0)))()
+                best = max(best, wide / float(ds * ds))
+                if kind == "up":
+                    ds //= 2
+        return best
+
+    def max_context_row_width(self):
+        """The widest buffer with one row per context token: the context itself, or the 4 ch wide k / v / k_ip / v_ip
+        projection of the widest SpatialTransformer (_context_kv)."""
+        down_path, middle, up_path = self._layout
+        chs = [a["ch"] for blk in list(down_path) + [middle] + list(up_path) for kind, a in blk if kind == "spatial"]
+        return max([self.context_dim or 0] + [4 * c for c in chs])
+
     def build_context_rows(self, context, B, T, tag="ctx"):
         """context fp32 [B, L, D] -> per-frame bf16 rows [B*T*Lc, D] (openaimodel3d.py:555-562)."""
         dev = context.device

@@ -271,6 +271,8 @@ class Arena:
         key = (tag, rows, cols, dtype)
         b = self._bufs.get(key)
         if b is None:
+            if rows * cols >= 2 ** 31:                  # the kernels index a buffer with 32-bit element offsets
+                raise ValueError(f"scratch buffer {tag} [{rows} x {cols}] has 2^31 elements or more")
             if self.guard:
                 G = self.GUARD
                 whole = torch.empty((rows + 2 * G, cols), dtype=dtype, device=device)
@@ -604,12 +606,15 @@ def embed_tokens(tokens, table, pos, out):
 
 
 def gemv_small(x, pw, out, *, act_in=0, act_out=0, accumulate=False):
-    """x [M<=8, K] fp32, out [M, N] fp32."""
-    if x.shape[0] > 8 or x.shape[1] < pw.K or out.shape[0] < x.shape[0] or out.shape[1] < pw.N:
+    """x [M, K] fp32, out [M, N] fp32; the kernel takes M <= 8 rows, more rows (the clips of a windowed UNet call) go in
+    launches of 8."""
+    if x.shape[1] < pw.K or out.shape[0] < x.shape[0] or out.shape[1] < pw.N:
         raise ValueError(f"gemv_small: x {tuple(x.shape)}, weight [{pw.N}, {pw.K}], out {tuple(out.shape)}")
-    check(_hip.lib().dc_gemv_small(_ptr(x), x.stride(0), _ptr(pw.w), _ptr(pw.bias), _ptr(out), out.stride(0),
-                                   x.shape[0], pw.N, pw.K, act_in, act_out, 1 if accumulate else 0, stream_ptr()),
-          "dc_gemv_small")
+    for r in range(0, x.shape[0], 8):
+        xs, os_ = x[r:r + 8], out[r:r + 8]
+        check(_hip.lib().dc_gemv_small(_ptr(xs), x.stride(0), _ptr(pw.w), _ptr(pw.bias), _ptr(os_), out.stride(0),
+                                       xs.shape[0], pw.N, pw.K, act_in, act_out, 1 if accumulate else 0, stream_ptr()),
+              "dc_gemv_small")
     return out
 
 
@@ -625,6 +630,59 @@ def pack_latent(x, cc, out, *, B, Cx, Cc, T, HW, nrep=1):
     _need(x, B * Cx * T * HW, "x"); _need(cc, B * Cc * T * HW, "c_concat"); _need_rows(out, nrep * B * T * HW, Cx + Cc, "out")
     check(_hip.lib().dc_pack_latent(_ptr(x), _ptr(cc), _ptr(out), B, Cx, Cc, T, HW, out.stride(0), nrep,
                                     stream_ptr()), "dc_pack_latent")
+    return out
+
+
+def window_tables(starts, wn, *, T_long, T, device):
+    """The device tables of a window plan (samplers/windows.py): starts int32 [S, W], wn fp32 [S, W, T]. The C entries
+    cannot look into device memory, so the values are checked here, on the host copy, before upload: every start in
+    [0, T_long - T], weights finite, >= 0 and summing to 1 on every frame of every step."""
+    import numpy as np
+    from .lvdm.models.samplers.windows import check_plan
+    starts = np.ascontiguousarray(starts, dtype=np.int32)
+    wn = np.ascontiguousarray(wn, dtype=np.float32)
+    S, W = check_plan(starts, wn, T_long, T)
+    return dict(starts=torch.from_numpy(starts).to(device), wn=torch.from_numpy(wn).to(device), S=S, W=W, T=int(T),
+                T_long=int(T_long), host_starts=starts, host_wn=wn)
+
+
+def _need_windows(plan, w0, n_w, index, step_index):
+    S, W, T = plan["S"], plan["W"], plan["T"]
+    if w0 < 0 or n_w < 1 or w0 + n_w > W:
+        raise ValueError(f"windows {w0} .. {w0 + n_w - 1} are not all in the plan's {W}")
+    if step_index is None and not 0 <= index < S:
+        raise ValueError(f"step {index} is outside the plan's {S} steps")
+    for t, dt, n, nm in ((plan["starts"], torch.int32, S * W, "starts"), (plan["wn"], torch.float32, S * W * T, "wn")):
+        if t.dtype != dt or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError(f"window plan: {nm} must be a contiguous CUDA {dt} tensor")
+        _need(t, n, nm)
+    return S, W, T
+
+
+def pack_latent_windows(x, cc, out, plan, *, B, Cx, Cc, HW, w0=0, n_w=None, index=0, step_index=None, nrep=1):
+    """pack_latent for the windows w0 .. w0 + n_w - 1 of the current step of `plan` (window_tables): rows
+    [(rep, b, w, f, p)][c_pad] (dc_pack_latent_windows). x, cc: fp32 [B, C, T_long, HW]."""
+    n_w = plan["W"] - w0 if n_w is None else n_w
+    S, W, T = _need_windows(plan, w0, n_w, index, step_index)
+    TL = plan["T_long"]
+    _need(x, B * Cx * TL * HW, "x"); _need(cc, B * Cc * TL * HW, "c_concat")
+    _rows(out, "out"); _need_rows(out, nrep * B * n_w * T * HW, Cx + Cc, "out")
+    check(_hip.lib().dc_pack_latent_windows(_ptr(x), _ptr(cc), _ptr(out), _ptr(plan["starts"]), _ptr(step_index), index,
+                                            S, W, w0, n_w, B, Cx, Cc, TL, T, HW, out.stride(0), nrep, stream_ptr()),
+          "dc_pack_latent_windows")
+    return out
+
+
+def window_merge(e, out, plan, *, nb, B, C, HW, w0=0, n_w=None, index=0, step_index=None, accumulate=False):
+    """out rows [(k, b, F, p)][ld_out] = the weighted blend of the window rows e [(k, b, w, f, p)][ld_e] of the windows
+    w0 .. w0 + n_w - 1 (dc_window_merge); accumulate adds to `out` (chunked evaluation, ascending chunks)."""
+    n_w = plan["W"] - w0 if n_w is None else n_w
+    S, W, T = _need_windows(plan, w0, n_w, index, step_index)
+    _rows(e, "e", torch.float32); _rows(out, "out", torch.float32)
+    _need_rows(e, nb * B * n_w * T * HW, C, "e"); _need_rows(out, nb * B * plan["T_long"] * HW, C, "out")
+    check(_hip.lib().dc_window_merge(_ptr(e), e.stride(0), _ptr(out), out.stride(0), _ptr(plan["starts"]),
+                                     _ptr(plan["wn"]), _ptr(step_index), index, S, W, w0, n_w, nb, B, C, plan["T_long"],
+                                     T, HW, 1 if accumulate else 0, stream_ptr()), "dc_window_merge")
     return out
 
 

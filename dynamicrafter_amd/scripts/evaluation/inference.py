@@ -57,7 +57,8 @@ def get_latent_z(model, videos):
 def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddim_steps=50, ddim_eta=1.,
                            unconditional_guidance_scale=1.0, cfg_img=None, fs=None, text_input=False,
                            multiple_cond_cfg=False, loop=False, interp=False, timestep_spacing="uniform",
-                           guidance_rescale=0.0, use_fixed_scheduler=False, sampler="ddim", **kwargs):
+                           guidance_rescale=0.0, use_fixed_scheduler=False, sampler="ddim", num_frames=None,
+                           window_stride=None, window_weights="triangle", window_shift=0, **kwargs):
     """inference.py:216-313. Returns [batch, n_samples, c, t, h, w] decoded frames.
 
     `use_fixed_scheduler` is accepted and ignored: the fork's "fixed" sampler only patches sigma so that
@@ -67,7 +68,25 @@ def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddi
     passes its **kwargs.
     `sampler` (not in the reference): "ddim" (default, the reference's sampler), or "dpmpp_2m" / "dpmpp_2m_sde" for
     DPM-Solver++ on the same timesteps (lvdm/models/samplers/dpm_solver.py; `ddim_steps` is then its step count and
-    `ddim_eta` is not used)."""
+    `ddim_eta` is not used).
+    `num_frames` (not in the reference): the clip's length in latent frames. Above the model's `temporal_length` the
+    sampler denoises overlapping windows of one long latent (lvdm/models/samplers/windows.py; `window_stride` defaults to
+    temporal_length // 2): the image latent is repeated over `num_frames` for c_concat, `x_T` / `noises` passed through
+    are `num_frames` long, and all frames are decoded. `window_stride` alone asks for windows at the clip's own length.
+    Not with `loop` / `interp`: their c_concat is zero on interior frames, so interior windows would see a conditioning
+    the model never met."""
+    T_model = getattr(model, "temporal_length", None)
+    if num_frames is not None:
+        if loop or interp:
+            raise ValueError(f"num_frames = {num_frames} cannot be combined with loop = {loop} / interp = {interp}: "
+                             f"windows inside the clip would be conditioned on all-zero c_concat frames")
+        if T_model is None or num_frames < T_model:
+            raise ValueError(f"num_frames = {num_frames} is below the model's temporal_length = {T_model}")
+        if num_frames > T_model and window_stride is None:
+            window_stride = T_model // 2
+        noise_shape = list(noise_shape[:2]) + [num_frames] + list(noise_shape[3:])
+    if window_stride is not None:
+        kwargs.update(window_stride=window_stride, window_weights=window_weights, window_shift=window_shift)
     if sampler == "ddim":
         ddim_sampler = DDIMSampler_multicond(model) if multiple_cond_cfg else DDIMSampler(model)
     elif sampler in DPM_SOLVERS:
@@ -93,7 +112,7 @@ def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddi
             img_cat_cond[:, :, 0] = z[:, :, 0]
             img_cat_cond[:, :, -1] = z[:, :, -1]
         else:
-            img_cat_cond = z[:, :, :1].repeat(1, 1, z.shape[2], 1, 1)
+            img_cat_cond = z[:, :, :1].repeat(1, 1, z.shape[2] if num_frames is None else num_frames, 1, 1)
         cond["c_concat"] = [img_cat_cond]
 
     if unconditional_guidance_scale != 1.0:

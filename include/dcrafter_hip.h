@@ -142,6 +142,33 @@ int dc_timestep_embedding(const int64_t* t_table, const int32_t* t_index, int t_
 int dc_pack_latent(const float* x, const float* cc, uint16_t* out, int B, int Cx, int Cc, int T, int HW,
                    int c_pad, int nrep, void* stream);
 
+/* dc_pack_latent for a set of overlapping T-frame windows of a clip of T_long > T frames (temporal co-denoising: the UNet
+ * denoises windows of one long latent, their outputs are blended where they overlap - dc_window_merge - and the sampler's
+ * update runs once on the long latent). x [B,Cx,T_long,H,W], cc [B,Cc,T_long,H,W] fp32 -> channels-last bf16 rows
+ * [(rep, b, w, f, p)][c_pad] for the windows w = w0 .. w0+n_w-1 of one step: frame f of window w is long frame
+ * starts[step*W + w] + f, channels >= Cx+Cc zeroed; (b, w) is the clip index of the UNet batch (B*n_w clips). starts: int32
+ * [S][W] device table, every entry in [0, T_long-T]; step = step_index[0] (device counter) or `index`, < S. The per-element
+ * conversion is dc_pack_latent's: for the gathered frames the rows are bit-identical to dc_pack_latent on a gathered tensor.
+ * no reference call site (the reference samples T frames only): MultiDiffusion, Bar-Tal et al., arXiv:2302.08113, applied
+ * along time as in Gen-L-Video, Wang et al., arXiv:2305.18264 */
+int dc_pack_latent_windows(const float* x, const float* cc, uint16_t* out, const int32_t* starts,
+                           const int32_t* step_index, int index, int S, int W, int w0, int n_w, int B, int Cx, int Cc,
+                           int T_long, int T, int HW, int c_pad, int nrep, void* stream);
+
+/* Blend of the UNet's window outputs onto the long clip. e: fp32 rows [(k, b, w, f, p)][ld_e] (nb branches k, n_w windows,
+ * first C channels valid) -> out: fp32 rows [(k, b, F, p)][ld_out], which dc_ddim_step / dc_dpmpp_step read as branch k at
+ * row offset k*B*T_long*HW with THW = T_long*HW:
+ *   out[k,b,F,p,c] = sum_w wn[(step*W + w)*T + F - starts[step*W + w]] * e[k,b,w,F - starts[step*W + w],p,c]
+ * over the windows w0 <= w < w0+n_w that contain F, summed in ascending w (first term a product, then fused multiply-adds);
+ * a term of weight 0 (padding window) is skipped and its e never read. Any two runs agree bitwise and a single window of
+ * weight 1 returns its input. accumulate == 0 writes (0 where no window of the call covers F), != 0 adds to what out holds:
+ * windows evaluated in chunks of n_w give the unchunked values (equal as numbers; a frame whose first term comes in a later
+ * chunk receives it through a multiply-add onto +0, so a -0 product becomes +0). wn: fp32 [S][W][T] device table, normalised so that the weights of the windows containing a frame sum to 1.
+ * no reference call site: arXiv:2302.08113 (eq. 5, the closed-form blend), arXiv:2305.18264 */
+int dc_window_merge(const float* e, int ld_e, float* out, int ld_out, const int32_t* starts, const float* wn,
+                    const int32_t* step_index, int index, int S, int W, int w0, int n_w, int nb, int B, int C, int T_long,
+                    int T, int HW, int accumulate, void* stream);
+
 /* Generic layout helpers (channels-last bf16 <-> NCHW fp32), used at the AutoencoderKL boundary.
  * nchw_to_rows: x[N][C][HW] fp32 -> rows[N*HW][c_pad] bf16 (scaled by `scale`, pad channels zero)
  * rows_to_nchw: rows[N*HW][ld] (bf16 or f32) -> y[N][C][HW] fp32 */
