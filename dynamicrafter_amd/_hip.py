@@ -113,6 +113,9 @@ SIGNATURES = {
     "dc_patchify": (_I, [_P, _P, _I, _I, _I, _I, _I, _I, _P]),
     "dc_embed_tokens": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _P]),
     "dc_frames_to_u8": (_I, [_P, _P, _I, _I, _I, _I, _I, _P]),
+    "dc_jpeg_dct_quant": (_I, [_P, _P, _P, _I, _I, _I, _P]),
+    "dc_jpeg_entropy": (_I, [_P, _P, _P, _I, _I, _I, _I, _L, _P]),
+    "dc_jpeg_pack": (_I, [_P, _P, _P, _P, _P, _I, _I, _L, _L, _P]),
     "dc_mask_blend": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _L, _L, _I, _P]),
     "dc_advance_counter": (_I, [_P, _P]),
     "dc_stream_create": (_I, [C.POINTER(_P)]),

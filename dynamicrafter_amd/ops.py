@@ -923,6 +923,63 @@ def advance_counter(counter):
     check(_hip.lib().dc_advance_counter(_ptr(counter), stream_ptr()), "dc_advance_counter")
 
 
+# ---------------------------------------------------------------------------------------------- baseline JPEG (csrc/jpeg.hip)
+JPEG_MCU_MAX_BYTES = 2496                       # DC_JPEG_MCU_MAX_BYTES of include/dcrafter_hip.h
+
+
+def _flat(t, dtype, name):
+    if not t.is_cuda or t.dtype != dtype or not t.is_contiguous():
+        raise ValueError(f"{name}: expected a contiguous CUDA {dtype} tensor, got {t.dtype} {tuple(t.shape)} on {t.device}")
+    return t
+
+
+def jpeg_mcu_grid(H, W):
+    return (H + 15) // 16, (W + 15) // 16
+
+
+def jpeg_dct_quant(frames, qtab, coef):
+    """frames uint8 [T, H, W, 3], qtab uint8 [2, 64] (zigzag order) -> coef int16 [T, my, mx, 6, 64] (zigzag order)."""
+    _flat(frames, torch.uint8, "frames"); _flat(qtab, torch.uint8, "qtab"); _flat(coef, torch.int16, "coef")
+    if frames.dim() != 4 or frames.shape[3] != 3:
+        raise ValueError(f"jpeg_dct_quant: frames [T, H, W, 3] expected, got {tuple(frames.shape)}")
+    T, H, W, _ = frames.shape
+    my, mx = jpeg_mcu_grid(H, W)
+    _need(qtab, 128, "qtab"); _need(coef, T * my * mx * 384, "coef")
+    _launch("jpeg_dct_quant", 0.0, frames.numel() + 2.0 * T * my * mx * 384, _hip.lib().dc_jpeg_dct_quant, _ptr(frames),
+            _ptr(qtab), _ptr(coef), T, H, W, stream_ptr())
+    return coef
+
+
+def jpeg_entropy(coef, scratch, seg_len, *, T, my, mx, ri, stride):
+    """coef int16 [T, my, mx, 6, 64] -> scratch uint8 [n_seg, stride], seg_len int32 [n_seg]; n_seg = T ceil(my mx / ri)."""
+    _flat(coef, torch.int16, "coef"); _flat(scratch, torch.uint8, "scratch"); _flat(seg_len, torch.int32, "seg_len")
+    if min(T, my, mx, ri) < 1:
+        raise ValueError(f"jpeg_entropy: T {T}, my {my}, mx {mx}, ri {ri}")
+    n_seg = T * ((my * mx + ri - 1) // ri)
+    if stride < min(ri, my * mx) * JPEG_MCU_MAX_BYTES + 1:
+        raise ValueError(f"jpeg_entropy: stride {stride} below the worst case of {min(ri, my * mx)} MCUs")
+    _need(coef, T * my * mx * 384, "coef"); _need(scratch, n_seg * stride, "scratch"); _need(seg_len, n_seg, "seg_len")
+    _launch("jpeg_entropy", 0.0, 2.0 * T * my * mx * 384, _hip.lib().dc_jpeg_entropy, _ptr(coef), _ptr(scratch), _ptr(seg_len),
+            T, my, mx, ri, stride, stream_ptr())
+    return n_seg
+
+
+def jpeg_pack(scratch, seg_len, seg_off, out, frame_len, *, T, segs_per_frame, stride, frame_stride):
+    """scratch [T segs_per_frame, stride] + seg_len -> out uint8 [T, frame_stride] (RSTm between a frame's segments),
+    frame_len int32 [T]; seg_off int32 [T segs_per_frame] is workspace."""
+    _flat(scratch, torch.uint8, "scratch"); _flat(out, torch.uint8, "out")
+    for t, name in ((seg_len, "seg_len"), (seg_off, "seg_off"), (frame_len, "frame_len")):
+        _flat(t, torch.int32, name)
+    if min(T, segs_per_frame, stride, frame_stride) < 1:
+        raise ValueError(f"jpeg_pack: T {T}, segs_per_frame {segs_per_frame}, stride {stride}, frame_stride {frame_stride}")
+    n_seg = T * segs_per_frame
+    _need(scratch, n_seg * stride, "scratch"); _need(seg_len, n_seg, "seg_len"); _need(seg_off, n_seg, "seg_off")
+    _need(out, T * frame_stride, "out"); _need(frame_len, T, "frame_len")
+    _launch("jpeg_pack(2 kernels)", 0.0, 0.0, _hip.lib().dc_jpeg_pack, _ptr(scratch), _ptr(seg_len), _ptr(seg_off), _ptr(out),
+            _ptr(frame_len), T, segs_per_frame, stride, frame_stride, stream_ptr())
+    return out
+
+
 class DeviceGraph:
     """hipGraph capture/replay of a block of dc_* calls issued on a private stream (runtime.hip)."""
 

@@ -4,9 +4,14 @@ Counterpart of the reference's `save_results` / `save_results_seperate` (scripts
 `tensor_to_mp4` (utils/save_video.py:27-43). Their arithmetic - clamp to [-1,1], (v+1)/2, x255, uint8 truncation, the
 n clips of a batch side by side (`make_grid(nrow=n, padding=0)`), frames as [t, h, w, c] - is one HIP kernel
 (`dc_frames_to_u8`) on the decoded tensor where it lies. The container differs: the reference hands the frames to
-torchvision.io.write_video (h264, crf 10); no video encoder exists in this image, so clips are written as APNG
+torchvision.io.write_video (h264, crf 10); no h264 encoder exists in this image, so by default clips are written as APNG
 (animated PNG: lossless, zlib only, one file per clip, plays in browsers) and single frames as PNG. File names keep the
 reference's stems; only the extension changes (.png instead of .mp4).
+
+`container="avi"` writes a video file instead: Motion-JPEG in an AVI container. The frames are encoded as baseline JPEG
+(T.81 SOF0, YCbCr 4:2:0, Annex K tables scaled by `quality` as libjpeg does, restart intervals) by three HIP launches on
+the uint8 frames where they lie (csrc/jpeg.hip: coefficients, entropy coding of one restart segment per wave, pack); only the
+packed scans travel to the host, which adds the JFIF headers and the RIFF structure.
 """
 import ctypes as C
 import os
@@ -16,7 +21,7 @@ import zlib
 import numpy as np
 import torch
 
-from .. import _hip
+from .. import _hip, ops
 from ..ops import stream_ptr
 
 
@@ -89,27 +94,205 @@ def write_apng(path, frames, fps=8, level=6, loops=0):
     return path
 
 
+# ---------------------------------------------------------------------------------------------- baseline JPEG / MJPEG AVI
+# ITU-T T.81 Annex K.1 / K.2 quantisation tables (natural, row-major order)
+_K1_LUMA = (16, 11, 10, 16, 24, 40, 51, 61, 12, 12, 14, 19, 26, 58, 60, 55, 14, 13, 16, 24, 40, 57, 69, 56,
+            14, 17, 22, 29, 51, 87, 80, 62, 18, 22, 37, 56, 68, 109, 103, 77, 24, 35, 55, 64, 81, 104, 113, 92,
+            49, 64, 78, 87, 103, 121, 120, 101, 72, 92, 95, 98, 112, 100, 103, 99)
+_K2_CHROMA = (17, 18, 24, 47, 99, 99, 99, 99, 18, 21, 26, 66, 99, 99, 99, 99, 24, 26, 56, 99, 99, 99, 99, 99,
+              47, 66, 99, 99, 99, 99, 99, 99) + (99,) * 32
+# zigzag scan (T.81 figure 5): JPEG_ZIGZAG[k] = 8 * row + col of the k-th coefficient
+JPEG_ZIGZAG = (0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21,
+               28, 35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54,
+               47, 55, 62, 63)
+# Annex K.3 - K.6 Huffman tables as DHT payloads (class/id byte, BITS, HUFFVAL), in the order libjpeg writes them; the kernels
+# carry the same tables (csrc/jpeg.hip)
+_AC_COMMON = ("535455565758595a636465666768696a737475767778797a", "92939495969798999aa2a3a4a5a6a7a8a9aab2b3b4b5b6b7b8b9bac2c3c4c5c6"
+              "c7c8c9cad2d3d4d5d6d7d8d9da")
+JPEG_DHT = (
+    bytes.fromhex("00" "00010501010101010100000000000000" "000102030405060708090a0b"),
+    bytes.fromhex("10" "0002010303020403050504040000017d" "01020300041105122131410613516107227114328191a1082342b1c11552d1f024"
+                  "33627282090a161718191a25262728292a3435363738393a434445464748494a" + _AC_COMMON[0] + "838485868788898a"
+                  + _AC_COMMON[1] + "e1e2e3e4e5e6e7e8e9eaf1f2f3f4f5f6f7f8f9fa"),
+    bytes.fromhex("01" "00030101010101010101010000000000" "000102030405060708090a0b"),
+    bytes.fromhex("11" "00020102040403040705040400010277" "000102031104052131061241510761711322328108144291a1b1c109233352f015"
+                  "6272d10a162434e125f11718191a262728292a35363738393a434445464748494a" + _AC_COMMON[0] + "82838485868788898a"
+                  + _AC_COMMON[1] + "e2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa"),
+)
+_JPEG_SCRATCH_BYTES = 256 << 20          # entropy-coding scratch per batch of frames (worst-case sized rows)
+
+
+def jpeg_quant_tables(quality):
+    """(natural, zigzag): the luminance and chrominance tables uint8 [2, 64] for `quality` in 1..100, row-major and in zigzag
+    order (as a DQT segment and the kernels hold them). Annex K scaled by libjpeg's rule: s = 5000 / q below 50, else
+    200 - 2 q; entry = clamp((base * s + 50) / 100, 1, 255), integer arithmetic."""
+    q = int(quality)
+    if not 1 <= q <= 100:
+        raise ValueError(f"JPEG quality must be in 1..100, got {quality}")
+    s = 5000 // q if q < 50 else 200 - 2 * q
+    nat = np.array([[min(max((b * s + 50) // 100, 1), 255) for b in base] for base in (_K1_LUMA, _K2_CHROMA)], dtype=np.uint8)
+    return nat, np.ascontiguousarray(nat[:, list(JPEG_ZIGZAG)])
+
+
+def _marker(m, payload):
+    return bytes((0xFF, m)) + struct.pack(">H", len(payload) + 2) + payload
+
+
+def jpeg_header(width, height, qtab_zigzag, restart_mcus):
+    """SOI, APP0 (JFIF 1.01), 2 x DQT, SOF0 (Y 2x2 / table 0, Cb and Cr 1x1 / table 1), 4 x DHT, DRI, SOS: everything in
+    front of the entropy-coded scan."""
+    out = b"\xff\xd8" + _marker(0xE0, b"JFIF\x00\x01\x01\x00\x00\x01\x00\x01\x00\x00")
+    for i in range(2):
+        out += _marker(0xDB, bytes((i,)) + bytes(bytearray(int(v) for v in qtab_zigzag[i])))
+    out += _marker(0xC0, struct.pack(">BHHB", 8, height, width, 3) + bytes((1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1)))
+    for t in JPEG_DHT:
+        out += _marker(0xC4, t)
+    out += _marker(0xDD, struct.pack(">H", restart_mcus))
+    return out + _marker(0xDA, bytes((3, 1, 0x00, 2, 0x11, 3, 0x11, 0, 63, 0)))
+
+
+def encode_jpeg_frames(frames_u8, quality=90, restart_mcus=None):
+    """frames_u8: uint8 [t, h, w, 3] on the GPU (what frames_to_uint8 returns) -> list of t complete JFIF files (bytes).
+    Baseline JPEG, YCbCr 4:2:0; `restart_mcus` = MCUs (16x16 pixels) per restart interval, i.e. per independently coded
+    segment (default 8, or the whole frame if it is smaller). Three launches per batch of frames, one device-to-host copy of
+    the packed scans."""
+    if not isinstance(frames_u8, torch.Tensor) or not frames_u8.is_cuda:
+        raise RuntimeError("encode_jpeg_frames runs on the HIP path only (there is no CPU fallback)")
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4:
+        raise ValueError(f"encode_jpeg_frames: uint8 [t, h, w, 3] expected, got {frames_u8.dtype} {tuple(frames_u8.shape)}")
+    if frames_u8.shape[3] != 3:
+        raise ValueError(f"encode_jpeg_frames: 3 channels expected, got {frames_u8.shape[3]} (APNG takes 1 and 4)")
+    f = frames_u8.contiguous()
+    t, h, w, _ = f.shape
+    if t < 1 or not (1 <= h <= 65535 and 1 <= w <= 65535):
+        raise ValueError(f"encode_jpeg_frames: frames of {h} x {w} x {t}")
+    my, mx = ops.jpeg_mcu_grid(h, w)
+    nmcu = my * mx
+    ri = min(8, nmcu) if restart_mcus is None else int(restart_mcus)
+    if not 1 <= ri <= 65535:
+        raise ValueError(f"restart_mcus must be in 1..65535, got {restart_mcus}")
+    _, qz = jpeg_quant_tables(quality)
+    header = jpeg_header(w, h, qz, ri)
+    dev = f.device
+    qtab = torch.from_numpy(qz).to(dev)
+    spf = (nmcu + ri - 1) // ri
+    stride = min(ri, nmcu) * ops.JPEG_MCU_MAX_BYTES + 1
+    tb = max(1, min(t, _JPEG_SCRATCH_BYTES // (spf * stride)))            # frames per batch
+    coef = torch.empty(tb * nmcu * 384, dtype=torch.int16, device=dev)
+    scratch = torch.empty(tb * spf * stride, dtype=torch.uint8, device=dev)
+    seg_len, seg_off = (torch.empty(tb * spf, dtype=torch.int32, device=dev) for _ in range(2))
+    frame_len = torch.empty(tb, dtype=torch.int32, device=dev)
+    frame_stride = nmcu * 384 + 2 * spf          # 1.5 bytes per pixel: a first guess far above typical frames, not a bound
+    out = torch.empty(tb * frame_stride, dtype=torch.uint8, device=dev)
+    files = []
+    for t0 in range(0, t, tb):
+        n = min(tb, t - t0)
+        ops.jpeg_dct_quant(f[t0:t0 + n], qtab, coef)
+        ops.jpeg_entropy(coef, scratch, seg_len, T=n, my=my, mx=mx, ri=ri, stride=stride)
+        ops.jpeg_pack(scratch, seg_len, seg_off, out, frame_len, T=n, segs_per_frame=spf, stride=stride, frame_stride=frame_stride)
+        lens = frame_len[:n].cpu().tolist()
+        if max(lens) > frame_stride:             # a frame outgrew the guess (the kernel dropped the excess): pack into wider rows
+            frame_stride = max(lens)
+            out = torch.empty(tb * frame_stride, dtype=torch.uint8, device=dev)
+            ops.jpeg_pack(scratch, seg_len, seg_off, out, frame_len, T=n, segs_per_frame=spf, stride=stride,
+                          frame_stride=frame_stride)
+        host = out[:n * frame_stride].view(n, frame_stride)[:, :max(lens)].cpu().numpy()
+        files += [header + host[i, :lens[i]].tobytes() + b"\xff\xd9" for i in range(n)]
+    return files
+
+
+def write_jpeg(path, frame_u8, quality=90):
+    """frame_u8: uint8 [h, w, 3] on the GPU -> one JFIF file."""
+    if not isinstance(frame_u8, torch.Tensor) or frame_u8.dim() != 3:
+        raise ValueError("write_jpeg: a uint8 [h, w, 3] GPU tensor expected")
+    data = encode_jpeg_frames(frame_u8[None], quality=quality)[0]
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as fh:
+        fh.write(data)
+    return path
+
+
+def _riff(tag, data):
+    return tag + struct.pack("<I", len(data)) + data + (b"\x00" if len(data) & 1 else b"")
+
+
+def _riff_list(kind, data):
+    return _riff(b"LIST", kind + data)
+
+
+def write_avi_mjpeg(path, jpeg_frames, width, height, fps):
+    """jpeg_frames: JFIF files (bytes) of width x height -> AVI 1.0 with one Motion-JPEG video stream at `fps` frames per
+    second (an integer: scale 1, rate fps). Layout: RIFF 'AVI ' { LIST hdrl { avih, LIST strl { strh, strf } }, LIST movi
+    { 00dc ... }, idx1 }; every frame is a key frame; idx1 offsets count from the 'movi' fourcc. Pure host code."""
+    frames = [bytes(f) for f in jpeg_frames]
+    rate = int(fps)
+    if not frames or rate < 1 or rate != fps or width < 1 or height < 1:
+        raise ValueError(f"write_avi_mjpeg: {len(frames)} frames of {width} x {height} at {fps} fps")
+    if any(f[:2] != b"\xff\xd8" for f in frames):
+        raise ValueError("write_avi_mjpeg: every frame must be a JPEG file (SOI first)")
+    n, biggest = len(frames), max(len(f) for f in frames)
+    avih = struct.pack("<14I", 1000000 // rate, biggest * rate, 0, 0x10, n, 0, 1, biggest, width, height, 0, 0, 0, 0)
+    strh = struct.pack("<4s4sIHHIIIIIIIIhhhh", b"vids", b"MJPG", 0, 0, 0, 0, 1, rate, 0, n, biggest, 0xFFFFFFFF, 0,
+                       0, 0, width, height)
+    strf = struct.pack("<IiiHH4sIiiII", 40, width, height, 1, 24, b"MJPG", width * height * 3, 0, 0, 0, 0)
+    hdrl = _riff_list(b"hdrl", _riff(b"avih", avih) + _riff_list(b"strl", _riff(b"strh", strh) + _riff(b"strf", strf)))
+    movi, idx, pos = [], [], 4                                   # pos: offset of the next chunk from the 'movi' fourcc
+    for f in frames:
+        ck = _riff(b"00dc", f)
+        idx.append(struct.pack("<4sIII", b"00dc", 0x10, pos, len(f)))      # AVIIF_KEYFRAME
+        movi.append(ck)
+        pos += len(ck)
+    body = b"AVI " + hdrl + _riff_list(b"movi", b"".join(movi)) + _riff(b"idx1", b"".join(idx))
+    if len(body) + 8 >= 1 << 32:
+        raise ValueError("write_avi_mjpeg: AVI 1.0 holds less than 4 GiB")
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as fh:
+        fh.write(b"RIFF" + struct.pack("<I", len(body)) + body)
+    return path
+
+
+def _write_clip(stem, grid, fps, container, quality):
+    """grid uint8 [t, h, w, c] on the GPU -> <stem>.png (APNG) or <stem>.avi (Motion-JPEG)."""
+    if container == "apng":
+        return write_apng(stem + ".png", grid, fps=fps)
+    if container == "avi":
+        return write_avi_mjpeg(stem + ".avi", encode_jpeg_frames(grid, quality=quality), grid.shape[2], grid.shape[1], fps)
+    raise ValueError(f"container must be 'apng' or 'avi', got {container!r}")
+
+
 # ---------------------------------------------------------------------------------------------- reference-named entry points
-def save_results(prompt, samples, filename, fakedir, fps=8, loop=False):
-    """inference.py:115-137: the batch as ONE clip, its n samples side by side. samples [n, c, t, h, w]."""
+def save_results(prompt, samples, filename, fakedir, fps=8, loop=False, container="apng", quality=90):
+    """inference.py:115-137: the batch as ONE clip, its n samples side by side. samples [n, c, t, h, w]. `container`: "apng"
+    (default, lossless) or "avi" (Motion-JPEG at JPEG `quality`)."""
     video = samples[:, :, :-1] if loop else samples            # loop mode drops the duplicated last frame
     grid = frames_to_uint8(video)
-    return write_apng(os.path.join(fakedir, filename.split(".")[0] + ".png"), grid, fps=fps)
+    return _write_clip(os.path.join(fakedir, filename.split(".")[0]), grid, fps, container, quality)
 
 
-def save_results_seperate(prompt, samples, filename, fakedir, fps=10, loop=False):
+def save_results_seperate(prompt, samples, filename, fakedir, fps=10, loop=False, container="apng", quality=90):
     """inference.py:140-162: one clip file per sample, under `samples_separate` (name kept as the reference spells it)."""
     video = samples[:, :, :-1] if loop else samples
     out = []
     d = fakedir.replace("samples", "samples_separate")
     for i in range(video.shape[0]):
         grid = frames_to_uint8(video[i:i + 1])
-        out.append(write_apng(os.path.join(d, f"{filename.split('.')[0]}_sample{i}.png"), grid, fps=fps))
+        out.append(_write_clip(os.path.join(d, f"{filename.split('.')[0]}_sample{i}"), grid, fps, container, quality))
     return out
 
 
-def tensor_to_frames(video, savedir, stem="frame"):
-    """One PNG per frame of a [n, c, t, h, w] batch laid out side by side (the still-image twin of tensor_to_mp4,
-    utils/save_video.py:27-43)."""
-    grid = frames_to_uint8(video).cpu().numpy()
-    return [write_png(os.path.join(savedir, f"{stem}_{i:04d}.png"), grid[i]) for i in range(grid.shape[0])]
+def tensor_to_frames(video, savedir, stem="frame", fmt="png", quality=90):
+    """One still per frame of a [n, c, t, h, w] batch laid out side by side (the still-image twin of tensor_to_mp4,
+    utils/save_video.py:27-43): PNG (default) or, with fmt="jpg", baseline JPEG at `quality`."""
+    grid = frames_to_uint8(video)
+    if fmt == "png":
+        grid = grid.cpu().numpy()
+        return [write_png(os.path.join(savedir, f"{stem}_{i:04d}.png"), grid[i]) for i in range(grid.shape[0])]
+    if fmt != "jpg":
+        raise ValueError(f"fmt must be 'png' or 'jpg', got {fmt!r}")
+    os.makedirs(os.path.abspath(savedir), exist_ok=True)
+    out = []
+    for i, data in enumerate(encode_jpeg_frames(grid, quality=quality)):
+        out.append(os.path.join(savedir, f"{stem}_{i:04d}.jpg"))
+        with open(out[-1], "wb") as fh:
+            fh.write(data)
+    return out

@@ -422,6 +422,41 @@ int dc_embed_tokens(const int64_t* tokens, const uint16_t* table, const uint16_t
  * utils/save_video.py:35-42 */
 int dc_frames_to_u8(const float* video, uint8_t* out, int N, int C, int T, int H, int W, void* stream);
 
+/* ---- baseline JPEG (T.81 SOF0, 8-bit, YCbCr 4:2:0, Annex K Huffman tables, restart intervals) for Motion-JPEG output ----
+ * Together the three entries stand where the reference hands its uint8 frames to a video encoder
+ * (torchvision.io.write_video: utils/save_video.py:27-43, scripts/evaluation/inference.py:115-162); the host adds the JFIF
+ * headers and the AVI container (dynamicrafter_amd/utils/save_video.py). An MCU is 16x16 pixels and holds the blocks
+ * Y00 Y01 Y10 Y11 Cb Cr; my = ceil(H/16), mx = ceil(W/16). */
+
+/* Upper bound of one entropy-coded MCU: 6 blocks x (22 + 63 x 26) bits = 1245 bytes, every one of them a stuffed 0xFF, plus
+ * the padded (and possibly stuffed) last byte of a segment. */
+#define DC_JPEG_MCU_MAX_BYTES 2496
+
+/* frames[T][H][W][3] uint8 (the layout dc_frames_to_u8 writes) -> quantised DCT coefficients coef[T][my][mx][6][64] int16 in
+ * zigzag order. fp32 throughout: Y = 0.299R + 0.587G + 0.114B, Cb = -0.168735892R - 0.331264108G + 0.5B + 128,
+ * Cr = 0.5R - 0.418687589G - 0.081312411B + 128, chroma = mean of its 2x2 pixels, level shift -128, orthonormal 2-D DCT-II,
+ * x = F / q (true division), coef = sign(x) floor(|x| + 0.5), AC clamped to +-1023. Pixels beyond the frame replicate its
+ * last row / column (any H, W >= 1). qtab[2][64] uint8 (device): luminance and chrominance tables in zigzag order, entries >= 1.
+ * replaces utils/save_video.py:27-43, scripts/evaluation/inference.py:115-162 (the encoder's transform stage) */
+int dc_jpeg_dct_quant(const uint8_t* frames, const uint8_t* qtab, int16_t* coef, int T, int H, int W, void* stream);
+
+/* coef[T][my][mx][6][64] -> one Huffman-coded byte string per restart segment of `ri` MCUs (the last of a frame may be
+ * shorter): scratch[n_seg][stride], seg_len[n_seg], n_seg = T * ceil(my*mx / ri), frames in order. Per segment the DC
+ * prediction starts from 0, 0xFF is followed by a stuffed 0x00 and the last byte is padded with 1-bits; no markers.
+ * stride >= min(ri, my*mx) * DC_JPEG_MCU_MAX_BYTES + 1, else DC_ERR_SHAPE. Coefficients outside DC -1024..1023 / AC +-1023
+ * are clamped to it.
+ * replaces utils/save_video.py:27-43, scripts/evaluation/inference.py:115-162 (the encoder's entropy stage) */
+int dc_jpeg_entropy(const int16_t* coef, uint8_t* scratch, int32_t* seg_len, int T, int my, int mx, int ri, int64_t stride,
+                    void* stream);
+
+/* Exclusive scan of each frame's segment lengths into seg_off[n_seg] (workspace), then a gather of the segments into one
+ * contiguous scan per frame, out[T][frame_stride], with RSTm (FF D0+m, m = the segment's index within its frame mod 8)
+ * between the segments of a frame and none after the last; frame_len[T] = the scan's length. Bytes beyond frame_stride are
+ * not written: a frame_len above frame_stride tells the caller to pack again into wider rows. T <= 65535.
+ * replaces utils/save_video.py:27-43, scripts/evaluation/inference.py:115-162 (the encoder's output stage) */
+int dc_jpeg_pack(const uint8_t* scratch, const int32_t* seg_len, int32_t* seg_off, uint8_t* out, int32_t* frame_len, int T,
+                 int segs_per_frame, int64_t stride, int64_t frame_stride, void* stream);
+
 /* Mask / x0 blend ahead of a DDIM step, in place on img [n] fp32: img = orig*mask + (1-mask)*img with
  * orig = x0 (clean != 0) or sqrt_acp_t[i]*x0 + sqrt_1macp_t[i]*qnoise (q_sample of x0 at the step's timestep);
  * i = step_index[0] (device counter; qnoise then starts at qnoise + i*noise_step_stride) or `index`.

@@ -1,0 +1,340 @@
+"""Motion-JPEG output on the GPU: the three dc_jpeg_* launches against the plain-Python restatement
+(tests/jpeg_restatement.py; its own standing against Pillow's codec is tests/test_mjpeg_cpu.py), the encoder end to end through
+Pillow's decoder, the save_results harness with container="avi", and the launches inside a captured graph.
+
+Inputs (np.random.default_rng(1) per case): "noise" = 0.6 N(0,1); "smooth" = sines and a checkerboard plus 0.05 N(0,1); both
+through clamp, (v + 1) / 2 * 255 and truncation; T = 2. Frame sizes: 40x72 (3x5 MCUs, both edges padded), 16x16 (one MCU),
+33x17 (a 1-pixel overhang both ways), 1x1."""
+import functools
+import io
+import struct
+
+import numpy as np
+import pytest
+import torch
+from PIL import Image
+
+from tests import jpeg_restatement as J
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+SIZES = [(40, 72), (16, 16), (33, 17), (1, 1)]
+KINDS = ["noise", "smooth"]
+SENT = 0xA5
+PSNR_MARGIN_DB = 0.25       # tests/test_mjpeg_cpu.py: five times the float64 restatement's largest shortfall against libjpeg
+_ids = lambda s: f"{s[0]}x{s[1]}" if isinstance(s, tuple) else str(s)
+
+
+@functools.lru_cache(maxsize=None)
+def _frames(kind, hw):
+    f = J.make_frames(kind, 2, hw[0], hw[1], np.random.default_rng(1))
+    f.setflags(write=False)
+    return f
+
+
+@functools.lru_cache(maxsize=None)
+def _ref_coef(kind, hw, q):
+    c = J.coefficients(_frames(kind, hw), J.quant_tables(q))
+    c.setflags(write=False)
+    return c
+
+
+def _gpu_coef(frames, q):
+    from dynamicrafter_amd import ops
+    from dynamicrafter_amd.utils import save_video as S
+    T, H, W, _ = frames.shape
+    my, mx = J.mcu_grid(H, W)
+    n = T * my * mx * 384
+    coef = torch.full((n + 64,), -7777, dtype=torch.int16, device=DEV)
+    qz = torch.from_numpy(S.jpeg_quant_tables(q)[1]).to(DEV)
+    ops.jpeg_dct_quant(torch.from_numpy(np.array(frames)).to(DEV), qz, coef)
+    torch.cuda.synchronize()
+    got = coef.cpu().numpy()
+    assert (got[n:] == -7777).all(), "dc_jpeg_dct_quant wrote past its output"
+    return got[:n].reshape(T, my, mx, 6, 64)
+
+
+# ------------------------------------------------------------------------------------------------ 1. coefficients
+@pytest.mark.parametrize("hw", SIZES, ids=_ids)
+@pytest.mark.parametrize("kind", KINDS)
+def test_coefficients_against_the_float64_restatement(kind, hw):
+    """At most 0.1 % of a case's coefficients may differ from the float64 restatement, none by more than 1: the room is for
+    rounding ties between two fp32 summation orders (a float32 restatement itself differs in none: test_mjpeg_cpu.py)."""
+    for q in (50, 90):
+        ref = _ref_coef(kind, hw, q)
+        got = _gpu_coef(_frames(kind, hw), q)
+        d = np.abs(got.astype(np.int32) - ref.astype(np.int32))
+        print(f"{kind} {hw} q{q}: {int((d != 0).sum())} of {d.size} coefficients differ, max |diff| {int(d.max())}")
+        assert d.max() <= 1
+        assert int((d != 0).sum()) <= d.size // 1000
+
+
+# ------------------------------------------------------------------------------------------------ 2. entropy coding + pack
+def _entropy_and_pack(coef, ri, frame_stride=None):
+    """Runs dc_jpeg_entropy and dc_jpeg_pack on coef int16 [T, my, mx, 6, 64] with sentinels behind every buffer; returns
+    (segments per frame as bytes, seg_len, scans per frame, stride)."""
+    from dynamicrafter_amd import ops
+    T, my, mx = coef.shape[:3]
+    nmcu = my * mx
+    spf = (nmcu + ri - 1) // ri
+    n_seg = T * spf
+    stride = min(ri, nmcu) * ops.JPEG_MCU_MAX_BYTES + 1
+    c = torch.from_numpy(np.ascontiguousarray(coef)).to(DEV)
+    scratch = torch.full((n_seg * stride + 64,), SENT, dtype=torch.uint8, device=DEV)
+    seg_len = torch.full((n_seg + 4,), -7, dtype=torch.int32, device=DEV)
+    seg_off = torch.full((n_seg + 4,), -7, dtype=torch.int32, device=DEV)
+    frame_len = torch.full((T + 4,), -7, dtype=torch.int32, device=DEV)
+    assert ops.jpeg_entropy(c, scratch, seg_len, T=T, my=my, mx=mx, ri=ri, stride=stride) == n_seg
+    torch.cuda.synchronize()
+    sl = seg_len.cpu().numpy()
+    assert (sl[n_seg:] == -7).all() and (sl[:n_seg] >= 0).all() and (sl[:n_seg] <= stride).all()
+    sc = scratch.cpu().numpy()
+    assert (sc[n_seg * stride:] == SENT).all(), "dc_jpeg_entropy wrote past the scratch buffer"
+    rows = sc[:n_seg * stride].reshape(n_seg, stride)
+    for i in range(n_seg):
+        assert (rows[i, sl[i]:] == SENT).all(), f"segment {i}: bytes written past seg_len"
+    segs = [[rows[t * spf + s, :sl[t * spf + s]].tobytes() for s in range(spf)] for t in range(T)]
+    lens = [sum(len(x) for x in fr) + 2 * (spf - 1) for fr in segs]
+    fs = frame_stride or max(lens)
+    out = torch.full((T * fs + 64,), SENT, dtype=torch.uint8, device=DEV)
+    ops.jpeg_pack(scratch, seg_len, seg_off, out, frame_len, T=T, segs_per_frame=spf, stride=stride, frame_stride=fs)
+    torch.cuda.synchronize()
+    fl = frame_len.cpu().numpy()
+    assert (fl[T:] == -7).all() and fl[:T].tolist() == lens
+    so = seg_off.cpu().numpy()
+    assert (so[n_seg:] == -7).all()
+    o = out.cpu().numpy()
+    assert (o[T * fs:] == SENT).all(), "dc_jpeg_pack wrote past its output"
+    o = o[:T * fs].reshape(T, fs)
+    for t in range(T):
+        assert (o[t, lens[t]:] == SENT).all(), f"frame {t}: bytes written past frame_len"
+    return segs, sl[:n_seg], [o[t, :min(lens[t], fs)].tobytes() for t in range(T)], stride
+
+
+def _check_entropy(coef, ri):
+    segs, sl, scans, stride = _entropy_and_pack(coef, ri)
+    for t in range(coef.shape[0]):
+        ref = J.entropy_segments(coef[t], ri)
+        assert len(ref) == len(segs[t])
+        for s, (a, b) in enumerate(zip(segs[t], ref)):
+            assert a == b, f"frame {t} segment {s} (ri {ri}): {len(a)} bytes, the restatement has {len(b)}"
+        assert scans[t] == J.join_segments(ref), f"frame {t} (ri {ri}): packed scan differs"
+    return sl, stride
+
+
+def _synthetic(name):
+    """Coefficient sets on a 3x5 MCU grid, T = 2."""
+    shape = (2, 3, 5, 6, 64)
+    c = np.zeros(shape, dtype=np.int16)
+    if name == "zeros":
+        pass
+    elif name == "last_only":                    # a single non-zero at zigzag index 63: DC, three ZRLs, run 14, no EOB
+        c[..., 63] = 1
+        c[1, ..., 63] = -3
+    elif name == "longest":                      # every AC +-1023; the DC of each component alternates -1024 / +1016 from
+        c[..., 1::2] = 1023                      # one of its blocks to the next: the longest codes and DC differences
+        c[..., 2::2] = -1023
+        m = np.arange(15).reshape(3, 5)
+        for b in range(4):
+            c[:, :, :, b, 0] = np.where((4 * m + b) % 2 == 0, -1024, 1016)
+        c[:, :, :, 4:, 0] = np.where(m % 2 == 0, -1024, 1016)[None, :, :, None]
+    elif name == "random":
+        c = np.random.default_rng(1).integers(-1023, 1024, size=shape).astype(np.int16)
+    return c
+
+
+@pytest.mark.parametrize("ri", [1, 3, "mx"])
+@pytest.mark.parametrize("hw", SIZES, ids=_ids)
+@pytest.mark.parametrize("kind", KINDS)
+def test_entropy_bit_exact_on_image_coefficients(kind, hw, ri):
+    """The kernel is fed the restatement's coefficients (test 1's cap cannot leak in). ri = 1 at 40x72 gives 15 segments per
+    frame, so RST7 wraps to RST0."""
+    coef = _ref_coef(kind, hw, 90)
+    ri = coef.shape[2] if ri == "mx" else ri
+    _check_entropy(coef, ri)
+    if hw == (40, 72) and ri == 1:
+        scan = J.entropy_scan(coef[0], 1)
+        assert b"\xff\xd7" in scan and scan.count(b"\xff\xd0") >= 2
+
+
+@pytest.mark.parametrize("ri", [1, 3, 5])
+@pytest.mark.parametrize("name", ["zeros", "last_only", "longest", "random"])
+def test_entropy_bit_exact_on_corner_cases(name, ri):
+    coef = _synthetic(name)
+    if name == "random":                                         # the stuffing path must really be exercised
+        assert any(b"\xff\x00" in s for t in range(2) for s in J.entropy_segments(coef[t], ri))
+    sl, stride = _check_entropy(coef, ri)
+    if name == "longest":
+        assert sl.max() <= stride
+        bits = 6 * 63 * 26                                       # every AC costs the full 16 + 10 bits
+        assert sl.max() * 8 > ri * bits
+        print(f"longest codes, ri {ri}: longest segment {sl.max()} bytes of stride {stride}")
+
+
+def test_pack_drops_what_does_not_fit_and_reports_the_full_length():
+    """frame_stride below a frame's length: nothing is written past the row, frame_len still tells the full length."""
+    coef = _synthetic("random")
+    full = [J.entropy_scan(coef[t], 3) for t in range(2)]
+    fs = min(len(x) for x in full) - 101
+    _, _, scans, _ = _entropy_and_pack(coef, 3, frame_stride=fs)              # asserts frame_len == the full lengths
+    assert [s for s in scans] == [x[:fs] for x in full]
+
+
+# ------------------------------------------------------------------------------------------------ 3. end to end
+def _decode(data):
+    im = Image.open(io.BytesIO(data))
+    im.load()
+    return im
+
+
+def _pillow_psnr(frame, q):
+    b = io.BytesIO()
+    Image.fromarray(frame).save(b, "JPEG", quality=q, subsampling=2, optimize=False)
+    return J.psnr(np.asarray(_decode(b.getvalue()).convert("RGB")), frame)
+
+
+@pytest.mark.parametrize("restart_mcus", [None, 3])
+@pytest.mark.parametrize("hw", SIZES, ids=_ids)
+@pytest.mark.parametrize("kind", KINDS)
+def test_encode_jpeg_frames_end_to_end(kind, hw, restart_mcus):
+    from dynamicrafter_amd.utils import save_video as S
+    H, W = hw
+    f = _frames(kind, hw)
+    g = torch.from_numpy(np.array(f)).to(DEV)
+    my, mx = J.mcu_grid(H, W)
+    for q in (50, 90) + ((100,) if kind == "noise" else ()):     # noise at q 100 outgrows the first row size of the pack
+        files = S.encode_jpeg_frames(g, quality=q, restart_mcus=restart_mcus)
+        assert len(files) == 2
+        for t, data in enumerate(files):
+            assert data[:2] == b"\xff\xd8" and data[-2:] == b"\xff\xd9"
+            ms = dict(J.markers(data))
+            assert ms[0xC0] == struct.pack(">BHHB", 8, H, W, 3) + bytes([1, 0x22, 0, 2, 0x11, 1, 3, 0x11, 1])
+            assert ms[0xDD] == struct.pack(">H", restart_mcus or min(8, my * mx))
+            im = _decode(data)
+            assert im.size == (W, H) and im.mode == "RGB"
+            ours, ref = J.psnr(np.asarray(im), f[t]), _pillow_psnr(f[t], q)
+            print(f"{kind} {H}x{W} q{q} frame {t}: {ours:.3f} dB, Pillow's encoder {ref:.3f} dB, {len(data)} bytes")
+            assert ours >= ref - PSNR_MARGIN_DB
+
+
+def test_encoder_refuses_what_it_cannot_code(tmp_path):
+    from dynamicrafter_amd.utils import save_video as S
+    with pytest.raises(ValueError):
+        S.encode_jpeg_frames(torch.zeros(1, 16, 16, 4, dtype=torch.uint8, device=DEV))
+    with pytest.raises(ValueError):
+        S.encode_jpeg_frames(torch.zeros(1, 16, 16, 1, dtype=torch.uint8, device=DEV))
+    with pytest.raises(ValueError):
+        S.encode_jpeg_frames(torch.zeros(1, 16, 16, 3, dtype=torch.uint8, device=DEV), restart_mcus=0)
+    with pytest.raises(RuntimeError):
+        S.encode_jpeg_frames(torch.zeros(1, 16, 16, 3, dtype=torch.uint8))
+    f = _frames("smooth", (33, 17))
+    p = S.write_jpeg(str(tmp_path / "a" / "one.jpg"), torch.from_numpy(np.array(f[0])).to(DEV), quality=90)
+    assert _decode(open(p, "rb").read()).size == (17, 33)
+
+
+# ------------------------------------------------------------------------------------------------ 4. harness
+def _samples(n=2, t=3, h=24, w=40):
+    g = torch.Generator().manual_seed(1)
+    return (torch.randn(n, 3, t, h, w, generator=g) * 0.5).to(DEV)
+
+
+def _avi_frames(path, size):
+    data = open(path, "rb").read()
+    r = J.walk_avi(data)
+    strh = struct.unpack("<4s4sIHHIIIIIIIIhhhh", r["chunks"]["hdrl/strl/strh"])
+    avih = struct.unpack("<14I", r["chunks"]["hdrl/avih"])
+    assert strh[1] == b"MJPG" and avih[4] == strh[9] == len(r["frames"]) == len(r["idx"]) and avih[8:10] == size
+    for (ckid, flags, off, n), fr in zip(r["idx"], r["frames"]):
+        at = r["movi"] + off
+        assert data[at:at + 4] == b"00dc" and data[at + 8:at + 8 + n] == fr
+        assert _decode(fr).size == size
+    return r["frames"], strh[7] / strh[6]
+
+
+def test_save_results_avi(tmp_path):
+    from dynamicrafter_amd.utils import save_video as S
+    x = _samples()
+    d = str(tmp_path / "samples")
+    p = S.save_results("a prompt", x, "clip0001.mp4", d, fps=8, container="avi", quality=90)
+    assert p.endswith("clip0001.avi")
+    frames, fps = _avi_frames(p, (2 * 40, 24))
+    assert len(frames) == 3 and fps == 8
+    grid = S.frames_to_uint8(x).cpu().numpy()
+    for t in range(3):
+        assert J.psnr(np.asarray(_decode(frames[t])), grid[t]) >= _pillow_psnr(grid[t], 90) - PSNR_MARGIN_DB
+    p = S.save_results("a prompt", x, "loop.mp4", d, fps=8, loop=True, container="avi")
+    assert len(_avi_frames(p, (80, 24))[0]) == 2
+    # the default still writes the APNG it wrote before
+    p = S.save_results("a prompt", x, "clip0001.mp4", d, fps=8)
+    assert p.endswith("clip0001.png")
+    ref = S.write_apng(str(tmp_path / "ref.png"), S.frames_to_uint8(x), fps=8)
+    assert open(p, "rb").read() == open(ref, "rb").read()
+    with pytest.raises(ValueError):
+        S.save_results("a prompt", x, "clip0001.mp4", d, container="mp4")
+
+
+def test_save_results_seperate_avi_and_jpg_frames(tmp_path):
+    from dynamicrafter_amd.utils import save_video as S
+    x = _samples()
+    d = str(tmp_path / "samples")
+    ps = S.save_results_seperate("a prompt", x, "clip0001.mp4", d, fps=10, container="avi", quality=50)
+    assert len(ps) == 2 and all("samples_separate" in p and p.endswith(f"_sample{i}.avi") for i, p in enumerate(ps))
+    for p in ps:
+        frames, fps = _avi_frames(p, (40, 24))
+        assert len(frames) == 3 and fps == 10
+    ps = S.save_results_seperate("a prompt", x, "clip0001.mp4", d, fps=10, loop=True, container="avi")
+    assert [len(_avi_frames(p, (40, 24))[0]) for p in ps] == [2, 2]
+    ps = S.save_results_seperate("a prompt", x, "clip0001.mp4", d, fps=10)
+    for i, p in enumerate(ps):
+        ref = S.write_apng(str(tmp_path / f"ref{i}.png"), S.frames_to_uint8(x[i:i + 1]), fps=10)
+        assert p.endswith(".png") and open(p, "rb").read() == open(ref, "rb").read()
+    js = S.tensor_to_frames(x, str(tmp_path / "stills"), fmt="jpg")
+    assert len(js) == 3 and all(p.endswith(".jpg") and _decode(open(p, "rb").read()).size == (80, 24) for p in js)
+    pn = S.tensor_to_frames(x, str(tmp_path / "stills"))
+    assert len(pn) == 3 and all(p.endswith(".png") for p in pn)
+
+
+# ------------------------------------------------------------------------------------------------ 5. capture
+def test_launches_replay_from_a_captured_graph():
+    """The three entries neither allocate nor synchronise: captured once into a graph, the replay on new frames gives the bytes
+    the eager launches give."""
+    from dynamicrafter_amd import ops
+    from dynamicrafter_amd.utils import save_video as S
+    hw, ri, q = (40, 72), 3, 90
+    T, (my, mx) = 2, J.mcu_grid(*hw)
+    spf = (my * mx + ri - 1) // ri
+    stride = ri * ops.JPEG_MCU_MAX_BYTES + 1
+    fs = my * mx * 384 + 2 * spf
+    frames = torch.from_numpy(np.array(_frames("smooth", hw))).to(DEV)
+    qz = torch.from_numpy(S.jpeg_quant_tables(q)[1]).to(DEV)
+    coef = torch.empty(T * my * mx * 384, dtype=torch.int16, device=DEV)
+    scratch = torch.empty(T * spf * stride, dtype=torch.uint8, device=DEV)
+    seg_len, seg_off = (torch.empty(T * spf, dtype=torch.int32, device=DEV) for _ in range(2))
+    frame_len = torch.empty(T, dtype=torch.int32, device=DEV)
+    out = torch.zeros(T * fs, dtype=torch.uint8, device=DEV)
+
+    def enqueue():
+        ops.jpeg_dct_quant(frames, qz, coef)
+        ops.jpeg_entropy(coef, scratch, seg_len, T=T, my=my, mx=mx, ri=ri, stride=stride)
+        ops.jpeg_pack(scratch, seg_len, seg_off, out, frame_len, T=T, segs_per_frame=spf, stride=stride, frame_stride=fs)
+
+    def result():
+        n = frame_len.cpu().tolist()
+        o = out.cpu().numpy().reshape(T, fs)
+        return [o[t, :n[t]].tobytes() for t in range(T)]
+
+    enqueue()
+    torch.cuda.synchronize()
+    eager_smooth = result()
+    graph = ops.DeviceGraph().capture(enqueue)
+    frames.copy_(torch.from_numpy(np.array(_frames("noise", hw))).to(DEV))      # new input in the captured buffers
+    out.zero_()
+    torch.cuda.synchronize()
+    graph.launch()
+    graph.sync()
+    replay_noise = result()
+    enqueue()
+    torch.cuda.synchronize()
+    assert replay_noise == result() and replay_noise != eager_smooth
+    header = S.jpeg_header(hw[1], hw[0], S.jpeg_quant_tables(q)[1], ri)
+    assert _decode(header + replay_noise[0] + b"\xff\xd9").size == (hw[1], hw[0])
