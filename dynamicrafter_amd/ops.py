@@ -980,6 +980,113 @@ def jpeg_pack(scratch, seg_len, seg_off, out, frame_len, *, T, segs_per_frame, s
     return out
 
 
+# ---------------------------------------------------------------------------------------------- image -> clip (csrc/preprocess.hip)
+RESIZE_PRECISION_BITS = 22                      # Pillow's PRECISION_BITS for 8-bit channels (32 - 8 - 2)
+
+
+def resize_coeffs(n_in, n_out):
+    """Pillow's BILINEAR resampling tables of one axis (Resample.c precompute_coeffs + normalize_coeffs_8bpc), on the host in
+    float64 with Pillow's operation order: k int32 [n_out, ksize], xmin int32 [n_out], n int32 [n_out] (numpy). The weights of
+    an output are summed tap by tap as Pillow sums them (numpy's pairwise sum would round differently)."""
+    import numpy as np
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in < 1 or n_out < 1:
+        raise ValueError(f"resize_coeffs: {n_in} -> {n_out}")
+    scale = n_in / n_out
+    filterscale = max(scale, 1.0)
+    support = 1.0 * filterscale                                   # the triangle filter's support is 1
+    ksize = int(math.ceil(support)) * 2 + 1
+    ss = 1.0 / filterscale
+    center = (np.arange(n_out, dtype=np.float64) + 0.5) * scale
+    xmin = np.maximum((center - support + 0.5).astype(np.int64), 0)            # the cast truncates, as C's (int) does
+    xmax = np.minimum((center + support + 0.5).astype(np.int64), n_in)
+    n = xmax - xmin
+    w = np.zeros((n_out, ksize), dtype=np.float64)
+    ww = np.zeros(n_out, dtype=np.float64)
+    for x in range(ksize):
+        a = np.abs((x + xmin - center + 0.5) * ss)
+        w[:, x] = np.where((a < 1.0) & (x < n), 1.0 - a, 0.0)
+        ww += w[:, x]
+    w = np.where((ww != 0.0)[:, None], w / np.where(ww != 0.0, ww, 1.0)[:, None], w)
+    k = (0.5 + w * float(1 << RESIZE_PRECISION_BITS)).astype(np.int32)          # weights are >= 0: truncation = C's (int)
+    k[np.arange(ksize)[None, :] >= n[:, None]] = 0
+    return k, xmin.astype(np.int32), n.astype(np.int32)
+
+
+class ResizeTables:
+    """Device copy of resize_coeffs(n_in, n_out) plus the host bounds the launch wrappers plan and check with. The kernels
+    trust the tables (include/dcrafter_hip.h), so this is where xmin + n <= n_in and n <= ksize are guaranteed."""
+
+    __slots__ = ("n_in", "n_out", "ksize", "k", "xmin", "n", "host_xmin", "host_n")
+
+    def __init__(self, n_in, n_out, device):
+        k, xmin, n = resize_coeffs(n_in, n_out)
+        if (xmin < 0).any() or (n < 0).any() or (n > k.shape[1]).any() or (xmin.astype("int64") + n > n_in).any():
+            raise AssertionError(f"resize tables {n_in} -> {n_out}: a window leaves the input")
+        self.n_in, self.n_out, self.ksize = int(n_in), int(n_out), int(k.shape[1])
+        self.host_xmin, self.host_n = xmin, n
+        self.k, self.xmin, self.n = (torch.from_numpy(a).to(device) for a in (k, xmin, n))
+
+    def span(self, lo, hi):
+        """(first, count) of the inputs that the outputs lo .. hi - 1 read."""
+        first = int(self.host_xmin[lo:hi].min())
+        return first, int((self.host_xmin[lo:hi] + self.host_n[lo:hi]).max()) - first
+
+
+def _image_u8(t, name):
+    _flat(t, torch.uint8, name)
+    if t.dim() != 3 or t.shape[2] != 3 or t.shape[0] < 1 or t.shape[1] < 1:
+        raise ValueError(f"{name}: uint8 [H, W, 3] expected, got {tuple(t.shape)}")
+    return t.shape[0], t.shape[1]
+
+
+def prep_resize_h(src, tmp, tab, *, y0, rows, x0, cols):
+    """Horizontal pass of src uint8 [H, W, 3] into tmp uint8 [rows, cols, 3] (workspace of the caller): source rows
+    y0 .. y0 + rows - 1, resized columns x0 .. x0 + cols - 1 (dc_prep_resize_h)."""
+    H, W = _image_u8(src, "src")
+    _flat(tmp, torch.uint8, "tmp")
+    if tab.n_in != W or tab.k.device != src.device or tmp.device != src.device:
+        raise ValueError(f"prep_resize_h: tables for width {tab.n_in} on {tab.k.device}, source width {W} on {src.device}")
+    if rows < 1 or cols < 1 or y0 < 0 or y0 + rows > H or x0 < 0 or x0 + cols > tab.n_out:
+        raise ValueError(f"prep_resize_h: rows {y0}+{rows} of {H}, columns {x0}+{cols} of {tab.n_out}")
+    _need(tmp, rows * cols * 3, "tmp")
+    _launch("prep_resize_h", 0.0, 3.0 * (rows * W + rows * cols), _hip.lib().dc_prep_resize_h, _ptr(src), _ptr(tmp), _ptr(tab.k),
+            _ptr(tab.xmin), _ptr(tab.n), tab.ksize, H, W, tab.n_out, y0, rows, x0, cols, stream_ptr())
+    return tmp
+
+
+def prep_finish(src, clip, tab, *, axis, src_hw, origin, resized, offset, t0, nt):
+    """The last pass (axis 0: none, 1: horizontal, 2: vertical; `tab` = its ResizeTables or None) + crop / padding / ToTensor /
+    Normalize into frames t0 .. t0 + nt - 1 of clip fp32 [3, T, ch, cw] (dc_prep_finish). src: uint8, `src_hw` pixels of 3
+    bytes whose first is pixel `origin` = (y, x) of its image; `resized` = (rh, rw); crop pixel (oy, ox) is the resized pixel
+    (oy + offset[0], ox + offset[1])."""
+    _flat(src, torch.uint8, "src"); _flat(clip, torch.float32, "clip")
+    if clip.dim() != 4 or clip.shape[0] != 3 or clip.device != src.device:
+        raise ValueError(f"prep_finish: clip fp32 [3, T, ch, cw] on {src.device} expected, got {tuple(clip.shape)} on {clip.device}")
+    _, T, ch, cw = clip.shape
+    (sh, sw), (sy0, sx0), (rh, rw), (yoff, xoff) = src_hw, origin, resized, offset
+    _need(src, sh * sw * 3, "src")
+    if nt < 1 or t0 < 0 or t0 + nt > T:
+        raise ValueError(f"prep_finish: frames {t0} .. {t0 + nt - 1} of {T}")
+    if axis not in (0, 1, 2) or (tab is None) != (axis == 0):
+        raise ValueError(f"prep_finish: axis {axis} with{'out' if tab is None else ''} tables")
+    ry0, ry1, rx0, rx1 = max(yoff, 0), min(ch + yoff, rh), max(xoff, 0), min(cw + xoff, rw)
+    if tab is not None:
+        if tab.k.device != src.device or tab.n_out != (rw if axis == 1 else rh):
+            raise ValueError(f"prep_finish: tables {tab.n_in} -> {tab.n_out} on {tab.k.device} for a resized image of {rh} x {rw}")
+        # the windows of every output the crop keeps lie inside src (the kernel trusts this)
+        lo, hi, s0, sn = (rx0, rx1, sx0, sw) if axis == 1 else (ry0, ry1, sy0, sh)
+        if lo < hi:
+            first, count = tab.span(lo, hi)
+            if first < s0 or first + count > s0 + sn:
+                raise ValueError(f"prep_finish: the pass reads inputs {first} .. {first + count - 1}, src holds {s0} .. {s0 + sn - 1}")
+    z = C.c_void_p(0)
+    _launch("prep_finish", 0.0, 3.0 * sh * sw + 12.0 * nt * ch * cw, _hip.lib().dc_prep_finish, _ptr(src), _ptr(clip),
+            z if tab is None else _ptr(tab.k), z if tab is None else _ptr(tab.xmin), z if tab is None else _ptr(tab.n),
+            0 if tab is None else tab.ksize, axis, sh, sw, sy0, sx0, rh, rw, yoff, xoff, ch, cw, T, t0, nt, stream_ptr())
+    return clip
+
+
 class DeviceGraph:
     """hipGraph capture/replay of a block of dc_* calls issued on a private stream (runtime.hip)."""
 

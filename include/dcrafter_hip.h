@@ -457,6 +457,40 @@ int dc_jpeg_entropy(const int16_t* coef, uint8_t* scratch, int32_t* seg_len, int
 int dc_jpeg_pack(const uint8_t* scratch, const int32_t* seg_len, int32_t* seg_off, uint8_t* out, int32_t* frame_len, int T,
                  int segs_per_frame, int64_t stride, int64_t frame_stride, void* stream);
 
+/* ---- image -> conditioning clip: Pillow's antialiased bilinear resize, centre crop / zero padding, ToTensor, Normalize ----
+ * Together the two entries stand where the reference's loader runs torchvision's Resize(min(video_size)) ->
+ * CenterCrop(video_size) -> ToTensor -> Normalize(0.5, 0.5) on a PIL image and repeats the result over the frames
+ * (scripts/evaluation/inference.py:71-76, 95-108). Resize on a PIL image is Image.resize(BILINEAR): per axis
+ *   out[xx] = clamp(((1 << 21) + sum_{i < n[xx]} in[xmin[xx] + i] * k[xx][i]) >> 22, 0, 255)      (int32, per channel)
+ * horizontal pass first, uint8 between the passes, a pass left out when its axis keeps its size.
+ * TABLES: k int32 [out][ksize], xmin int32 [out], n int32 [out] are device memory built on the host in float64 with Pillow's
+ * operation order (dynamicrafter_amd/ops.py resize_coeffs). They are TRUSTED: the entries cannot read them without a
+ * synchronisation, so it is the ops.py wrapper that guarantees xmin + n <= in and n <= ksize for every output, and that the
+ * rows of an intermediate cover every window of the vertical pass. (A window that breaks this is cut to the operand inside the
+ * kernel: wrong pixels, no read outside it.)
+ * Neither entry allocates or synchronises; both check their arguments before any launch. */
+
+/* Horizontal pass of src uint8 [H][W][3] into the intermediate dst uint8 [rows][cols][3]: source rows y0 .. y0 + rows - 1
+ * (the ones the vertical pass reads), resized columns x0 .. x0 + cols - 1 of out_w (the ones the crop keeps).
+ * replaces scripts/evaluation/inference.py:73 (transforms.Resize, horizontal pass), applied at :97, :99, :106 */
+int dc_prep_resize_h(const uint8_t* src, uint8_t* dst, const int32_t* k, const int32_t* xmin, const int32_t* n, int ksize, int H,
+                     int W, int out_w, int y0, int rows, int x0, int cols, void* stream);
+
+/* The last pass, fused with crop, padding, normalisation and the repetition over frames. src uint8 [sh][sw][3] is a part of an
+ * image whose pixel (sy0, sx0) is src's (0, 0); the resized image is rh x rw; crop pixel (oy, ox) of ch x cw is the resized
+ * pixel (oy + yoff, ox + xoff), or padding (uint8 0) where that lies outside the resized image.
+ *   axis 0: no pass (src is the resized image);  k, kmin, kn may be NULL
+ *   axis 1: horizontal pass (src has the resized height; tables per resized column)
+ *   axis 2: vertical pass (src has the resized width: the source, or dc_prep_resize_h's intermediate; tables per resized row)
+ * Then v = u8 / 255, (v - 0.5) / 0.5 in fp32, stored into frames t0 .. t0 + nt - 1 of clip fp32 [3][T][ch][cw]; other frames
+ * are not touched (the reference's interp mode: the first image into frames 0 .. T/2 - 1, the second into the rest).
+ * DC_ERR_SHAPE unless src holds, along the axis it is addressed directly, every resized pixel the crop keeps.
+ * replaces scripts/evaluation/inference.py:73-76 (Resize's last pass, CenterCrop, ToTensor, Normalize) and :95-108
+ * (unsqueeze / repeat over video_frames / cat of the two halves) */
+int dc_prep_finish(const uint8_t* src, float* clip, const int32_t* k, const int32_t* kmin, const int32_t* kn, int ksize, int axis,
+                   int sh, int sw, int sy0, int sx0, int rh, int rw, int yoff, int xoff, int ch, int cw, int T, int t0, int nt,
+                   void* stream);
+
 /* Mask / x0 blend ahead of a DDIM step, in place on img [n] fp32: img = orig*mask + (1-mask)*img with
  * orig = x0 (clean != 0) or sqrt_acp_t[i]*x0 + sqrt_1macp_t[i]*qnoise (q_sample of x0 at the step's timestep);
  * i = step_index[0] (device counter; qnoise then starts at qnoise + i*noise_step_stride) or `index`.
