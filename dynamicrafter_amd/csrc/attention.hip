@@ -13,16 +13,12 @@
 //   (clip, position, head)); reference: TemporalTransformer.forward attention.py:365-412 -> CrossAttention :81-144.
 #include "dc_common.h"
 #include "dcrafter_hip.h"
+#include "lds_stage.h"
 #include <stdlib.h>
 #include <type_traits>
 
 namespace {
 
-typedef __attribute__((address_space(3))) bf16x4_t lds_bf16x4_t;
-
-__device__ __forceinline__ int k_lds_off(int row, int chunk) {
-    return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4);
-}
 constexpr int V_LD = 192;  // bytes per V row in LDS: 4 consecutive rows land on 4 distinct 64-byte bank quarters
 
 constexpr int FA_BQ = 128;   // query rows per workgroup
@@ -101,7 +97,7 @@ __global__ __launch_bounds__(256, 2) void flash_attn_d64_kernel(
 #pragma unroll
         for (int i = 0; i < 2; ++i) {
             const int r = srow + 32 * i;
-            *reinterpret_cast<u32x4_t*>(sk + k_lds_off(r, chunk)) = kreg[i];
+            *reinterpret_cast<u32x4_t*>(sk + lds_off128(r, chunk)) = kreg[i];
             *reinterpret_cast<u32x4_t*>(sv + r * V_LD + chunk * 16) = vreg[i];
         }
     };
@@ -153,7 +149,7 @@ __global__ __launch_bounds__(256, 2) void flash_attn_d64_kernel(
         for (int jb = 0; jb < 2; ++jb)
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk) {
-                const bf16x8_t kf = *reinterpret_cast<const bf16x8_t*>(sk + k_lds_off(jb * 32 + fr, kk * 2 + fh));
+                const bf16x8_t kf = *reinterpret_cast<const bf16x8_t*>(sk + lds_off128(jb * 32 + fr, kk * 2 + fh));
 #pragma unroll
                 for (int x = 0; x < QB; ++x)
                     s[x][jb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[x][kk], s[x][jb], 0, 0, 0);
@@ -354,10 +350,10 @@ __global__ __launch_bounds__(256, 2) void cross_attn_resident_kernel(
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
             const int r = srow + 32 * i;
-            *reinterpret_cast<u32x4_t*>(smem + XA_K1 + k_lds_off(r, chunk)) = kr[i];
+            *reinterpret_cast<u32x4_t*>(smem + XA_K1 + lds_off128(r, chunk)) = kr[i];
             *reinterpret_cast<u32x4_t*>(smem + XA_V1 + r * V_LD + chunk * 16) = vr[i];
         }
-        *reinterpret_cast<u32x4_t*>(smem + XA_K2 + k_lds_off(srow, chunk)) = kr[3];
+        *reinterpret_cast<u32x4_t*>(smem + XA_K2 + lds_off128(srow, chunk)) = kr[3];
         *reinterpret_cast<u32x4_t*>(smem + XA_V2 + srow * V_LD + chunk * 16) = vr[3];
     }
     const int li = lane & 15;
@@ -383,7 +379,7 @@ __global__ __launch_bounds__(256, 2) void cross_attn_resident_kernel(
             for (int r = 0; r < 16; ++r) s[jb][r] = 0.f;
 #pragma unroll
             for (int kk = 0; kk < 4; ++kk) {
-                const bf16x8_t kf = *reinterpret_cast<const bf16x8_t*>(sk + k_lds_off(jb * 32 + fr, kk * 2 + fh));
+                const bf16x8_t kf = *reinterpret_cast<const bf16x8_t*>(sk + lds_off128(jb * 32 + fr, kk * 2 + fh));
                 s[jb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf, qf[kk], s[jb], 0, 0, 0);
             }
         }
@@ -456,10 +452,10 @@ __global__ __launch_bounds__(256, 2) void cross_attn_resident_kernel(
         for (int d = 0; d < 2; ++d)
 #pragma unroll
             for (int r = 0; r < 16; ++r) { o1[d][r] = 0.f; o2[d][r] = 0.f; }
-        const float l1 = scores(smem + XA_K1, Lk, std::integral_constant<int, 3>{}, s, qf);
-        pv_mma(smem + XA_V1, std::integral_constant<int, 3>{}, s, o1);
-        const float l2 = scores(smem + XA_K2, Lk2, std::integral_constant<int, 1>{}, s, qf);
-        pv_mma(smem + XA_V2, std::integral_constant<int, 1>{}, s, o2);
+        const float l1 = scores(smem + XA_K1, Lk, ic<3>{}, s, qf);
+        pv_mma(smem + XA_V1, ic<3>{}, s, o1);
+        const float l2 = scores(smem + XA_K2, Lk2, ic<1>{}, s, qf);
+        pv_mma(smem + XA_V2, ic<1>{}, s, o2);
         const float w1 = 1.0f / l1, w2 = acc_scale / l2;
         // store: a row's channels 8 qd .. 8 qd + 7 are split over its two lanes; one v_permlane32_swap per dword between the
         // groups qd and qd + 1 gives each lane 16 contiguous bytes

@@ -38,6 +38,7 @@
 // (DESIGN.md section 3.2 has the per-phase stamps).
 #include "dc_common.h"
 #include "dcrafter_hip.h"
+#include "lds_stage.h"
 #include <stdint.h>
 #include <type_traits>
 
@@ -54,10 +55,6 @@ constexpr int W2_RING = 3;
 constexpr int FF_LDS = 2 * W1_STAGE + W2_RING * W2_STAGE + 4 * 2048 + 2 * FM * 4;    // rings + epilogue patches + b1 (fp32)
 static_assert(FF_LDS <= 160 * 1024, "LDS");
 
-typedef __attribute__((address_space(3))) char lds_char_t;
-typedef __attribute__((address_space(3))) bf16x4_t lds_bf16x4_t;
-typedef const volatile __attribute__((address_space(3))) bf16x8_t lds_vfrag_t;   // pinned LDS fragment load (see PD)
-__device__ __attribute__((aligned(16))) uint32_t g_zero_ff[8];
 #ifdef DC_FF_STAMPS          // tool build only (tools/ff_stamps.py): shader-clock totals of the four parts of a chunk iteration
 __device__ unsigned long long g_ff_stamps[8];
 #define FF_STAMP(i) do { asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory"); const unsigned long long t__ = __builtin_readcyclecounter(); \
@@ -71,19 +68,6 @@ __device__ unsigned long long g_ff_stamps[8];
 #else
 #define FF_GELU(x) gelu_phi_f(x)      // the last chunk's stand-alone GEGLU: the same function as the interleaved stream
 #endif
-__device__ __forceinline__ int off128(int row, int chunk) { return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4); }
-__device__ __forceinline__ int off64(int row, int chunk) { return row * 64 + ((chunk ^ ((row >> 2) & 3)) << 4); }
-
-__device__ __forceinline__ void glds16f(const void* gsrc, unsigned lds_dst_uniform) {
-    asm volatile(
-        "s_mov_b32 m0, %1\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %0, off"
-        :
-        : "v"(gsrc), "s"(lds_dst_uniform)
-        : "memory");
-}
-
 
 // LayerNorm of the rows held as X fragments (lanes (fr, 0) and (fr, 1) hold the two halves of row fr), two-pass in
 // registers (BasicTransformerBlock norm1/2/3, lvdm/modules/attention.py:225-227, eps 1e-5); the result is rounded to bf16
@@ -219,28 +203,17 @@ void ff_geglu_fused320_kernel(const FfParams p) {
     for (int i = 0; i < 10; ++i) asm volatile("" : "+v"(vo1[i]));    // opaque: or hipcc re-derives the wave-uniform parts
 #pragma unroll                                                       // in the main loop (5 scalar instructions per piece)
     for (int i = 0; i < 5; ++i) asm volatile("" : "+v"(vo2[i]));
-    auto dma_piece = [&](unsigned lds_dst, unsigned voff, uint64_t sbase) __attribute__((always_inline)) {
-        // (m0 is NOT saved and restored around a piece: nothing else in these kernels uses it - checked in the ISA, as for gemm_pipe16.h - and
-        //  two scalar moves per piece are 8-10 issue clocks of a one-wave-per-SIMD stream)
-        asm volatile(
-            "s_mov_b32 m0, %0\n\t"
-            "s_nop 0\n\t"
-            "global_load_lds_dwordx4 %1, %2"
-            :
-            : "s"(lds_dst), "v"(voff), "s"(sbase)
-            : "memory");
-    };
     auto w1_base = [&](int j) { return (uint64_t)(uintptr_t)p.W1 + (uint64_t)j * (FCH * FD * 2); };
     auto w2_base = [&](int j) { return (uint64_t)(uintptr_t)p.W2p + (uint64_t)j * (FCH * 2); };
     auto w1_dst = [&](int j, int i) { return lds_base + (j & 1) * W1_STAGE + (wave * 10 + i) * 1024; };
     auto w2_dst = [&](int stage, int i) { return lds_base + 2 * W1_STAGE + stage * W2_STAGE + (wave * 5 + i) * 1024; };
     auto issue_w1 = [&](int j) __attribute__((always_inline)) {
 #pragma unroll
-        for (int i = 0; i < 10; ++i) dma_piece(w1_dst(j, i), vo1[i], w1_base(j));
+        for (int i = 0; i < 10; ++i) lds_dma16_sbase(w1_dst(j, i), vo1[i], w1_base(j));
     };
     auto issue_w2 = [&](int j, int stage) __attribute__((always_inline)) {
 #pragma unroll
-        for (int i = 0; i < 5; ++i) dma_piece(w2_dst(stage, i), vo2[i], w2_base(j));
+        for (int i = 0; i < 5; ++i) lds_dma16_sbase(w2_dst(stage, i), vo2[i], w2_base(j));
     };
 
 #ifdef DC_FF_STAMPS
@@ -278,8 +251,8 @@ void ff_geglu_fused320_kernel(const FfParams p) {
             bf16x8_t wv[PD], wg[PD];
             auto rd1 = [&](int kk, int slot) __attribute__((always_inline)) {
                 const char* kt = s1 + (kk >> 2) * 8192;
-                wv[slot] = *(lds_vfrag_t*)((lds_char_t*)kt + off128(fr, (kk & 3) * 2 + fh));
-                wg[slot] = *(lds_vfrag_t*)((lds_char_t*)kt + off128(32 + fr, (kk & 3) * 2 + fh));
+                wv[slot] = *(lds_vfrag_t*)((lds_char_t*)kt + lds_off128(fr, (kk & 3) * 2 + fh));
+                wg[slot] = *(lds_vfrag_t*)((lds_char_t*)kt + lds_off128(32 + fr, (kk & 3) * 2 + fh));
             };
 #pragma unroll
             for (int kk = 0; kk < PD; ++kk) rd1(kk, kk);
@@ -316,13 +289,13 @@ void ff_geglu_fused320_kernel(const FfParams p) {
         };
         // phase 2 of chunk c (W2 ring stage st): out[row][ch] += P W2c^T (W2 packed in the matching k order). DW1 / DW2:
         // the wave's LDS-DMA pieces of W1(jd + 2) / W2(jd + 1) go out one behind each of the first MFMAs.
-        const int a2_0 = off64(fr, fh), a2_1 = off64(fr, 2 + fh);
+        const int a2_0 = lds_off64(fr, fh), a2_1 = lds_off64(fr, 2 + fh);
         auto phase2 = [&](int st, const bf16x8_t (&pf)[2], auto DW1, auto DW2, int jd, int st_next) __attribute__((always_inline)) {
             const char* s2 = w2s + st * W2_STAGE;
             bf16x8_t w2r[PD2];
             auto rd2 = [&](int idx, int slot) __attribute__((always_inline)) {      // idx = s * 10 + nb
                 const int s = idx / (FD / 32), nb = idx % (FD / 32);
-                // off64(nb * 32 + fr, s * 2 + fh) = nb * 2048 + (fr * 64 + swizzled chunk): nb only moves an immediate offset,
+                // lds_off64(nb * 32 + fr, s * 2 + fh) = nb * 2048 + (fr * 64 + swizzled chunk): nb only moves an immediate offset,
                 // two lane-dependent bases cover all 20 fragments (spelled out: hipcc kept 20 address registers otherwise)
                 w2r[slot] = *(lds_vfrag_t*)((lds_char_t*)s2 + (s ? a2_1 : a2_0) + nb * 2048);
             };
@@ -336,8 +309,8 @@ void ff_geglu_fused320_kernel(const FfParams p) {
                 if (idx + PD2 < 2 * (FD / 32)) rd2(idx + PD2, idx % PD2);
                 asm volatile("" : "+v"(cw));
                 acc[nb] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cw, pf[s], acc[nb], 0, 0, 0);
-                if (DW1.value && idx < 10) dma_piece(w1_dst(jd + 2, idx), vo1[idx], b1n);
-                if (DW2.value && idx >= 10 && idx < 15) dma_piece(w2_dst(st_next, idx - 10), vo2[idx - 10], b2n);
+                if (DW1.value && idx < 10) lds_dma16_sbase(w1_dst(jd + 2, idx), vo1[idx], b1n);
+                if (DW2.value && idx >= 10 && idx < 15) lds_dma16_sbase(w2_dst(st_next, idx - 10), vo2[idx - 10], b2n);
             }
         };
         // phase 1 of chunk c + 1 and the GEGLU of chunk c in ONE hand-interleaved instruction stream. One wave per SIMD
@@ -356,8 +329,8 @@ void ff_geglu_fused320_kernel(const FfParams p) {
             bf16x8_t wv[PD], wg[PD];
             auto rd1 = [&](int kk, int slot) __attribute__((always_inline)) {
                 const char* kt = s1 + (kk >> 2) * 8192;
-                wv[slot] = *(lds_vfrag_t*)((lds_char_t*)kt + off128(fr, (kk & 3) * 2 + fh));
-                wg[slot] = *(lds_vfrag_t*)((lds_char_t*)kt + off128(32 + fr, (kk & 3) * 2 + fh));
+                wv[slot] = *(lds_vfrag_t*)((lds_char_t*)kt + lds_off128(fr, (kk & 3) * 2 + fh));
+                wg[slot] = *(lds_vfrag_t*)((lds_char_t*)kt + lds_off128(32 + fr, (kk & 3) * 2 + fh));
             };
 #pragma unroll
             for (int kk = 0; kk < PD; ++kk) rd1(kk, kk);
@@ -472,7 +445,7 @@ void ff_geglu_fused320_kernel(const FfParams p) {
         typedef std::integral_constant<bool, false> no_t;
         __builtin_amdgcn_s_barrier();                    // every wave is done with the previous tile's LDS stages
         issue_w1(0);
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory"); // W1(0) (and the X fragments)
+        wait_vmcnt<0>(); // W1(0) (and the X fragments)
         __builtin_amdgcn_s_barrier();
         asm volatile("" ::: "memory");
         issue_w1(1);
@@ -482,7 +455,7 @@ void ff_geglu_fused320_kernel(const FfParams p) {
         phase1(0, a0, a0g);
         auto top = [&]() __attribute__((always_inline)) {
             FF_STAMP(4);
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vmcnt<0>();
             __builtin_amdgcn_s_barrier();
             asm volatile("" ::: "memory");
             FF_STAMP(0);
@@ -590,17 +563,17 @@ void ff_geglu_fused320_kernel(const FfParams p) {
             // Wp in chunks of 32 output channels (20 KB: 5 K tiles of [32 rows][128 B]) through two stages of the (idle) W2
             // ring, 5 LDS-DMA pieces per wave, one chunk ahead; counted waits: a chunk's pieces are followed by the previous
             // chunk's residual loads (2, already consumed) and stores (2)
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vmcnt<0>();
             __builtin_amdgcn_s_barrier();                // every wave is done reading the W rings of the FeedForward
             asm volatile("" ::: "memory");
             auto wp_base = [&](int c) { return (uint64_t)(uintptr_t)p.Wp + (uint64_t)c * (32 * FD * 2); };
             auto wp_dst = [&](int c, int i) { return lds_base + 2 * W1_STAGE + (c & 1) * W2_STAGE + (wave * 5 + i) * 1024; };
 #pragma unroll
-            for (int i = 0; i < 5; ++i) dma_piece(wp_dst(0, i), vo3[i], wp_base(0));
+            for (int i = 0; i < 5; ++i) lds_dma16_sbase(wp_dst(0, i), vo3[i], wp_base(0));
             const bool full_tile = tile * FBM + FBM <= p.M;
             for (int c = 0; c < FD / 32; ++c) {
-                if (c == 0 || !full_tile) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
+                if (c == 0 || !full_tile) wait_vmcnt<0>();
+                else wait_vmcnt<4>();
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
                 const char* s3 = w2s + (c & 1) * W2_STAGE;
@@ -610,7 +583,7 @@ void ff_geglu_fused320_kernel(const FfParams p) {
                 constexpr int PD3 = 6;
                 bf16x8_t wr[PD3];
                 auto rd3 = [&](int kk, int sl) __attribute__((always_inline)) {
-                    wr[sl] = *(lds_vfrag_t*)((lds_char_t*)s3 + (kk >> 2) * 4096 + off128(fr_e, (kk & 3) * 2 + fh_e));
+                    wr[sl] = *(lds_vfrag_t*)((lds_char_t*)s3 + (kk >> 2) * 4096 + lds_off128(fr_e, (kk & 3) * 2 + fh_e));
                 };
 #pragma unroll
                 for (int kk = 0; kk < PD3; ++kk) rd3(kk, kk);
@@ -622,7 +595,7 @@ void ff_geglu_fused320_kernel(const FfParams p) {
                     if (kk + PD3 < FD / 16) rd3(kk + PD3, kk % PD3);
                     asm volatile("" : "+v"(f));
                     ya = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f, xf[kk], ya, 0, 0, 0);
-                    if (kk < 5 && more) dma_piece(wp_dst(c + 1, kk), vo3[kk], nbase);
+                    if (kk < 5 && more) lds_dma16_sbase(wp_dst(c + 1, kk), vo3[kk], nbase);
                 }
                 // chunk epilogue: + bp, bf16, + R2, row-major through the wave-private patch (32 rows x 64 B)
                 const int n0 = c * 32;
@@ -654,7 +627,7 @@ void ff_geglu_fused320_kernel(const FfParams p) {
                     if (mrow[t] < p.M) *reinterpret_cast<u32x4_t*>(p.O2 + (size_t)mrow[t] * p.ldo2 + n0 + rc * 8) = d;
                 }
             }
-            asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+            wait_vmcnt<0>();
         }
     }
 #ifdef DC_FF_STAMPS
@@ -730,22 +703,11 @@ void norm_linear_kernel(const LlParams p) {
         vo[i] = (unsigned)((g * 8 + (lane >> 3)) * (KD * 2) + t * 128 + (((lane & 7) ^ ((g * 4 + (lane >> 4)) & 7)) << 4));
         asm volatile("" : "+v"(vo[i]));
     }
-    auto dma_piece = [&](unsigned lds_dst, unsigned voff, uint64_t sbase) __attribute__((always_inline)) {
-        // (m0 is NOT saved and restored around a piece: nothing else in these kernels uses it - checked in the ISA, as for gemm_pipe16.h - and
-        //  two scalar moves per piece are 8-10 issue clocks of a one-wave-per-SIMD stream)
-        asm volatile(
-            "s_mov_b32 m0, %0\n\t"
-            "s_nop 0\n\t"
-            "global_load_lds_dwordx4 %1, %2"
-            :
-            : "s"(lds_dst), "v"(voff), "s"(sbase)
-            : "memory");
-    };
     auto w_base = [&](int c, int h) { return (uint64_t)(uintptr_t)p.W + (uint64_t)c * (LCH * KD * 2) + h * (FD * 2); };
     auto w_dst = [&](int slot, int i) { return lds_base + slot * LW_STAGE + (wave * 5 + i) * 1024; };
 
 #pragma unroll
-    for (int i = 0; i < 5; ++i) dma_piece(w_dst(0, i), vo[i], w_base(c_begin, 0));
+    for (int i = 0; i < 5; ++i) lds_dma16_sbase(w_dst(0, i), vo[i], w_base(c_begin, 0));
 
     // ---- X fragments of this wave's 32 rows (B operand: lane (row fr, half fh) holds k = 16 kk + 8 fh .. + 7)
     bf16x8_t xf[KD / 16];
@@ -788,9 +750,9 @@ void norm_linear_kernel(const LlParams p) {
         for (int h = 0; h < KH; ++h) {
             if (c > c_begin || h > 0) {
                 // this stage was issued during the previous one, in front of that stage's two stores if it closed a chunk
-                if (!full_tile) asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-                else if (h == 0) asm volatile("s_waitcnt vmcnt(2)" ::: "memory");
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                if (!full_tile) wait_vmcnt<0>();
+                else if (h == 0) wait_vmcnt<2>();
+                else wait_vmcnt<0>();
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
             }
@@ -809,7 +771,7 @@ void norm_linear_kernel(const LlParams p) {
             const char* s1 = smem + slot * LW_STAGE;
             bf16x8_t wr[PD];
             auto rd = [&](int kk, int sl) __attribute__((always_inline)) {
-                wr[sl] = *(lds_vfrag_t*)((lds_char_t*)s1 + (kk >> 2) * 4096 + off128(fr, (kk & 3) * 2 + fh));
+                wr[sl] = *(lds_vfrag_t*)((lds_char_t*)s1 + (kk >> 2) * 4096 + lds_off128(fr, (kk & 3) * 2 + fh));
             };
 #pragma unroll
             for (int kk = 0; kk < PD; ++kk) rd(kk, kk);
@@ -821,7 +783,7 @@ void norm_linear_kernel(const LlParams p) {
                 if (kk + PD < FD / 16) rd(kk + PD, kk % PD);
                 asm volatile("" : "+v"(f));
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f, xf[h * (FD / 16) + kk], acc, 0, 0, 0);
-                if (kk < 5 && more) dma_piece(w_dst(slot ^ 1, kk), vo[kk], nb);
+                if (kk < 5 && more) lds_dma16_sbase(w_dst(slot ^ 1, kk), vo[kk], nb);
             }
             slot ^= 1;
         }
@@ -926,17 +888,6 @@ void ln_qkv_tattn_kernel(const TaParams p) {
         vo[i] = (unsigned)((g * 8 + (lane >> 3)) * (KD * 2) + t * 128 + (((lane & 7) ^ ((g * 4 + (lane >> 4)) & 7)) << 4));
         asm volatile("" : "+v"(vo[i]));
     }
-    auto dma_piece = [&](unsigned lds_dst, unsigned voff, uint64_t sbase) __attribute__((always_inline)) {
-        // (m0 is NOT saved and restored around a piece: nothing else in these kernels uses it - checked in the ISA, as for gemm_pipe16.h - and
-        //  two scalar moves per piece are 8-10 issue clocks of a one-wave-per-SIMD stream)
-        asm volatile(
-            "s_mov_b32 m0, %0\n\t"
-            "s_nop 0\n\t"
-            "global_load_lds_dwordx4 %1, %2"
-            :
-            : "s"(lds_dst), "v"(voff), "s"(sbase)
-            : "memory");
-    };
     // chunk (head h, part): part 0,1 = q halves, 2,3 = k halves, 4,5 = v halves -> weight rows (part/2) * C + 64 h + 32 (part&1);
     // stage (chunk, kh): the k half kh of those rows
     auto w_base = [&](int h, int part, int kh) {
@@ -951,7 +902,7 @@ void ln_qkv_tattn_kernel(const TaParams p) {
 #pragma unroll
     for (int d = 0; d < NS - 1; ++d)
 #pragma unroll
-        for (int i = 0; i < 5; ++i) dma_piece(w_dst(d, i), vo[i], w_base(h_begin + d / SPH, (d % SPH) / KH, d % KH));
+        for (int i = 0; i < 5; ++i) lds_dma16_sbase(w_dst(d, i), vo[i], w_base(h_begin + d / SPH, (d % SPH) / KH, d % KH));
 
     bf16x8_t xf[KD / 16];
     {
@@ -986,18 +937,18 @@ void ln_qkv_tattn_kernel(const TaParams p) {
                     const int rem = (h + 1 == h_end) ? SPH - 1 - lin : NS;         // stages behind this one (>= NS - 2 is all that matters)
                     const int younger = rem < NS - 2 ? rem : NS - 2;
                     const int n = 5 * younger + ((lin == 0) ? 4 : 0);
-                    if (n >= 14) asm volatile("s_waitcnt vmcnt(14)" ::: "memory");
-                    else if (n >= 10) asm volatile("s_waitcnt vmcnt(10)" ::: "memory");
-                    else if (n >= 5) asm volatile("s_waitcnt vmcnt(5)" ::: "memory");
-                    else if (n >= 4) asm volatile("s_waitcnt vmcnt(4)" ::: "memory");
-                    else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                    if (n >= 14) wait_vmcnt<14>();
+                    else if (n >= 10) wait_vmcnt<10>();
+                    else if (n >= 5) wait_vmcnt<5>();
+                    else if (n >= 4) wait_vmcnt<4>();
+                    else wait_vmcnt<0>();
                     __builtin_amdgcn_s_barrier();
                     asm volatile("" ::: "memory");
                 }
                 const char* s1 = smem + slot * LW_STAGE;
                 bf16x8_t wr[PD];
                 auto rd = [&](int kk, int sl) __attribute__((always_inline)) {
-                    wr[sl] = *(lds_vfrag_t*)((lds_char_t*)s1 + (kk >> 2) * 4096 + off128(fr, (kk & 3) * 2 + fh));
+                    wr[sl] = *(lds_vfrag_t*)((lds_char_t*)s1 + (kk >> 2) * 4096 + lds_off128(fr, (kk & 3) * 2 + fh));
                 };
 #pragma unroll
                 for (int kk = 0; kk < PD; ++kk) rd(kk, kk);
@@ -1012,7 +963,7 @@ void ln_qkv_tattn_kernel(const TaParams p) {
                     if (kk + PD < FD / 16) rd(kk + PD, kk % PD);
                     asm volatile("" : "+v"(f));
                     acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f, xf[kh * (FD / 16) + kk], acc, 0, 0, 0);
-                    if (kk < 5 && more) dma_piece(w_dst(nl % NS, kk), vo[kk], nb);
+                    if (kk < 5 && more) lds_dma16_sbase(w_dst(nl % NS, kk), vo[kk], nb);
                 }
             }
             if (part < 4) {
@@ -1092,14 +1043,14 @@ void ln_qkv_tattn_kernel(const TaParams p) {
                 uint2 pk;
                 pk.x = pack_bf2(oacc[db][4 * q], oacc[db][4 * q + 1]);
                 pk.y = pack_bf2(oacc[db][4 * q + 2], oacc[db][4 * q + 3]);
-                *reinterpret_cast<uint2*>(vpatch + off128(fr, 4 * db + q) + fh * 8) = pk;
+                *reinterpret_cast<uint2*>(vpatch + lds_off128(fr, 4 * db + q) + fh * 8) = pk;
             }
         {
             const int rrow = lane >> 3, rc = lane & 7;
 #pragma unroll
             for (int t = 0; t < 4; ++t) {
                 const int r = t * 8 + rrow;
-                const u32x4_t d = *reinterpret_cast<const u32x4_t*>(vpatch + off128(r, rc));
+                const u32x4_t d = *reinterpret_cast<const u32x4_t*>(vpatch + lds_off128(r, rc));
                 *reinterpret_cast<u32x4_t*>(p.O + grow(r) * p.ldo + 64 * h + rc * 8) = d;
             }
         }
@@ -1166,17 +1117,6 @@ void gn_silu_tconv_kernel(const TcParams p) {
         vo[i] = (unsigned)((g * 8 + (lane >> 3)) * (3 * KD * 2) + t * 384 + (((lane & 7) ^ ((g * 4 + (lane >> 4)) & 7)) << 4));
         asm volatile("" : "+v"(vo[i]));
     }
-    auto dma_piece = [&](unsigned lds_dst, unsigned voff, uint64_t sbase) __attribute__((always_inline)) {
-        // (m0 is NOT saved and restored around a piece: nothing else in these kernels uses it - checked in the ISA, as for gemm_pipe16.h - and
-        //  two scalar moves per piece are 8-10 issue clocks of a one-wave-per-SIMD stream)
-        asm volatile(
-            "s_mov_b32 m0, %0\n\t"
-            "s_nop 0\n\t"
-            "global_load_lds_dwordx4 %1, %2"
-            :
-            : "s"(lds_dst), "v"(voff), "s"(sbase)
-            : "memory");
-    };
     // stage index within a chunk: j = 0 .. 3 KH - 1, tap = order[j / KH], half = j % KH
     auto w_base = [&](int c, int j) {
         const int jt = j / KH, h = j - jt * KH;
@@ -1186,7 +1126,7 @@ void gn_silu_tconv_kernel(const TcParams p) {
     auto w_dst = [&](int slot, int i) { return lds_base + slot * LW_STAGE + (wave * 5 + i) * 1024; };
 
 #pragma unroll
-    for (int i = 0; i < 5; ++i) dma_piece(w_dst(0, i), vo[i], w_base(c_begin, 0));
+    for (int i = 0; i < 5; ++i) lds_dma16_sbase(w_dst(0, i), vo[i], w_base(c_begin, 0));
 
     bf16x8_t xf[KD / 16];
     {
@@ -1216,8 +1156,8 @@ void gn_silu_tconv_kernel(const TcParams p) {
             const int jt = j / KH, h = j % KH;            // jt 0: tap 1 (centre) -> out; 1: tap 0 (frame - 1); 2: tap 2 (frame + 1)
             if (c > c_begin || j > 0) {
                 // this stage was issued during the previous one, in front of the loads / stores that closed a chunk
-                if (j == 0) { if (RES && KH != 1) asm volatile("s_waitcnt vmcnt(4)" ::: "memory"); else asm volatile("s_waitcnt vmcnt(2)" ::: "memory"); }
-                else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
+                if (j == 0) { if (RES && KH != 1) wait_vmcnt<4>(); else wait_vmcnt<2>(); }
+                else wait_vmcnt<0>();
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
             }
@@ -1238,7 +1178,7 @@ void gn_silu_tconv_kernel(const TcParams p) {
             }
             bf16x8_t wr[PD];
             auto rd = [&](int kk, int sl) __attribute__((always_inline)) {
-                wr[sl] = *(lds_vfrag_t*)((lds_char_t*)s1 + (kk >> 2) * 4096 + off128(fr, (kk & 3) * 2 + fh));
+                wr[sl] = *(lds_vfrag_t*)((lds_char_t*)s1 + (kk >> 2) * 4096 + lds_off128(fr, (kk & 3) * 2 + fh));
             };
 #pragma unroll
             for (int kk = 0; kk < PD; ++kk) rd(kk, kk);
@@ -1250,7 +1190,7 @@ void gn_silu_tconv_kernel(const TcParams p) {
                 if (kk + PD < FD / 16) rd(kk + PD, kk % PD);
                 asm volatile("" : "+v"(f));
                 acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f, xf[h * (FD / 16) + kk], acc, 0, 0, 0);
-                if (kk < 5 && more) dma_piece(w_dst(slot ^ 1, kk), vo[kk], nb);
+                if (kk < 5 && more) lds_dma16_sbase(w_dst(slot ^ 1, kk), vo[kk], nb);
             }
             slot ^= 1;
             if (jt > 0 && h == KH - 1) {

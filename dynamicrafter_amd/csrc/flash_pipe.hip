@@ -39,14 +39,11 @@
 // (XOR-swizzled rows), V^T fragments by ds_read_b64_tr_b16.
 #include "dc_common.h"
 #include "dcrafter_hip.h"
+#include "lds_stage.h"
 #include <type_traits>
 #include <stdlib.h>
 
 namespace {
-
-typedef __attribute__((address_space(3))) char lds_char_t;
-typedef __attribute__((address_space(3))) bf16x4_t lds_bf16x4_t;
-typedef const volatile __attribute__((address_space(3))) bf16x8_t lds_vfrag_t;
 
 constexpr int FP_VLD = 192;                 // bytes per V row in LDS (4 consecutive rows on 4 distinct 64-byte bank quarters)
 constexpr int FP_KBYTES = 64 * 128;
@@ -55,8 +52,6 @@ constexpr int FP_STAGE = FP_KBYTES + FP_VBYTES;     // 20 KB
 constexpr int FP_NSTAGE = 4;
 constexpr int FP_RING = FP_NSTAGE * FP_STAGE;       // 80 KB
 constexpr int FP_LDS = FP_RING + 64;                // + the arrival counter of the ring
-
-template <int V> using ic = std::integral_constant<int, V>;
 
 // tool builds only (tools/flash_variants.sh): switch parts of the main loop off to see what bounds it; results are wrong
 #ifdef FP_DBG_NOEX
@@ -258,7 +253,7 @@ void flash_attn_d64_pipe_kernel(const bf16_t* __restrict__ q, const bf16_t* __re
     // complete - it is first requested right there - and its requests of tile T-1 have returned.
     // In-gap order: the MFMA, this gap's two v_exp_f32, then the pack of the PREVIOUS gap's exponentials, v_max3 in between -
     // no statement directly follows one that produced an operand of it (hipcc pads such pairs of asm statements).
-    __attribute__((address_space(3))) int* const ring_cnt = (__attribute__((address_space(3))) int*)(smem + FP_RING);
+    lds_int_t* const ring_cnt = (lds_int_t*)(smem + FP_RING);
     int seen = 0, gave_up = 0;
     auto step = [&](auto PAR_, auto TR_, auto DEC_, auto QK_, auto MX_, auto EX_, auto PV_, auto NK_, auto NV_, auto RING_,
                     const unsigned (&kn)[4], int knpar, unsigned vn, int vnpar, int tile, int stage) __attribute__((always_inline)) {
@@ -296,13 +291,9 @@ void flash_attn_d64_pipe_kernel(const bf16_t* __restrict__ q, const bf16_t* __re
             // ends; the bound (about 10 ms, once per wave) keeps a future bookkeeping mistake from hanging the GPU: the wave then
             // carries on with whatever the ring holds and the kernel reports DC_ERRW_FLASH_RING in the error word
             if constexpr (RING == 2) {
-                if (g == NEX - 4) seen = *(volatile __attribute__((address_space(3))) int*)ring_cnt;
+                if (g == NEX - 4) seen = *(volatile lds_int_t*)ring_cnt;
                 if (j == 0) {
-                    int spins = 0;
-                    while (!gave_up && __builtin_amdgcn_readfirstlane(seen) < tile) {
-                        seen = *(volatile __attribute__((address_space(3))) int*)ring_cnt;
-                        if (++spins > 200000) gave_up = 1;
-                    }
+                    LDS_SPIN(__builtin_amdgcn_readfirstlane(seen) < tile, seen = *(volatile lds_int_t*)ring_cnt);
                     asm volatile("" ::: "memory");
                 }
             }

@@ -18,6 +18,7 @@
 // ds_read_b128 fragment reads.
 #include "dc_common.h"
 #include "dcrafter_hip.h"
+#include "lds_stage.h"
 #include <stdlib.h>
 
 namespace {
@@ -25,16 +26,6 @@ namespace {
 constexpr int BM = 128;
 constexpr int BK = 64;
 constexpr int NTHREADS = 256;
-
-__device__ __forceinline__ int lds_off(int row, int chunk) {
-    // 128-byte rows, 16-byte chunks; XOR the chunk with bits of the row so that 16 rows (distinct mod 16)
-    // reading the same logical chunk hit 16 distinct 16-byte slots of the 256-byte bank row.
-    return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4);
-}
-
-// 32 zero bytes in device memory: padded taps / tail rows load from here, so every global load of the main loop is
-// unconditional (a branch around a load makes hipcc wait for it at the join: four serialised round trips per tile).
-__device__ __attribute__((aligned(16))) uint32_t g_zero_chunk[8];
 
 template <int BN, bool GEGLU, int MODE>
 __global__ __launch_bounds__(NTHREADS) void gemm_conv_kernel(const DcGemmParams p) {
@@ -155,9 +146,9 @@ __global__ __launch_bounds__(NTHREADS) void gemm_conv_kernel(const DcGemmParams 
         char* sa = smem + buf * STAGE;
         char* sb = sa + A_BYTES;
 #pragma unroll
-        for (int i = 0; i < 4; ++i) *reinterpret_cast<u32x4_t*>(sa + lds_off(srow + 32 * i, chunk)) = a_reg[i];
+        for (int i = 0; i < 4; ++i) *reinterpret_cast<u32x4_t*>(sa + lds_off128(srow + 32 * i, chunk)) = a_reg[i];
 #pragma unroll
-        for (int i = 0; i < B_ITERS; ++i) *reinterpret_cast<u32x4_t*>(sb + lds_off(srow + 32 * i, chunk)) = b_reg[i];
+        for (int i = 0; i < B_ITERS; ++i) *reinterpret_cast<u32x4_t*>(sb + lds_off128(srow + 32 * i, chunk)) = b_reg[i];
     };
 
     f32x16_t acc[2][NB];
@@ -186,13 +177,13 @@ __global__ __launch_bounds__(NTHREADS) void gemm_conv_kernel(const DcGemmParams 
             bf16x8_t xf[2], wf[NB];
 #pragma unroll
             for (int mb = 0; mb < 2; ++mb)
-                xf[mb] = *reinterpret_cast<const bf16x8_t*>(sa + lds_off(wm * 64 + mb * 32 + fr, kk * 2 + fh));
+                xf[mb] = *reinterpret_cast<const bf16x8_t*>(sa + lds_off128(wm * 64 + mb * 32 + fr, kk * 2 + fh));
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) {
                 int brow;
                 if (GEGLU) brow = nb * (BN / 2) + wn * 32 + fr;      // nb 0 = value half, nb 1 = gate half
                 else brow = wn * (32 * NB) + nb * 32 + fr;
-                wf[nb] = *reinterpret_cast<const bf16x8_t*>(sb + lds_off(brow, kk * 2 + fh));
+                wf[nb] = *reinterpret_cast<const bf16x8_t*>(sb + lds_off128(brow, kk * 2 + fh));
             }
 #pragma unroll
             for (int mb = 0; mb < 2; ++mb)
@@ -434,7 +425,7 @@ __global__ __launch_bounds__(256, 2) void conv3x3_window128_kernel(const DcGemmP
     extern __shared__ __attribute__((aligned(16))) char wsm[];
     char* const win = wsm;
     char* const wst = wsm + WC_WIN_BYTES;
-    const unsigned lds_base = (unsigned)(uintptr_t)((const __attribute__((address_space(3))) char*)wsm);
+    const unsigned lds_base = (unsigned)(uintptr_t)((const lds_char_t*)wsm);
     const int tid = threadIdx.x, lane = tid & 63;
     const int wave = __builtin_amdgcn_readfirstlane(tid >> 6);
     const int lj = lane & 15, lq = lane >> 4;
@@ -482,10 +473,10 @@ __global__ __launch_bounds__(256, 2) void conv3x3_window128_kernel(const DcGemmP
             const bool in = px < NC_WIN && iy >= 0 && iy < p.IH && ix >= 0 && ix < p.IW;
             const uint16_t* src = in ? fbase + ((size_t)iy * p.IW + ix) * p.lda + sl * 64 + ch * 8
                                      : reinterpret_cast<const uint16_t*>(g_zero_chunk);
-            asm volatile("s_mov_b32 m0, %1\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %0, off" ::"v"(src), "s"(lds_base + g * 1024) : "memory");
+            lds_dma16(src, lds_base + g * 1024);
         }
         w_store();                                      // tap 0 of this slice (fetched during the previous slice's last tap)
-        asm volatile("s_waitcnt vmcnt(0)" ::: "memory");    // this wave's window pieces have landed (hipcc does not count asm DMA)
+        wait_vmcnt<0>();                                     // this wave's window pieces have landed (hipcc does not count asm DMA)
         __syncthreads();
 #pragma unroll 1
         for (int t = 0; t < 9; ++t) {

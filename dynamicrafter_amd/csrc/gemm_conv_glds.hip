@@ -14,6 +14,7 @@
 // lane-linear (base + lane*16), the swizzle is applied to the per-lane SOURCE address.
 #include "dc_common.h"
 #include "dcrafter_hip.h"
+#include "lds_stage.h"
 #include <stdint.h>
 #include <stdlib.h>
 #include <type_traits>
@@ -27,33 +28,6 @@ constexpr int GNT = 512;
 // Tile shapes (BN x stages): 128 x 3, 256 x 2 and 320 x 2. The wider tiles exist because the per-CU vector-memory
 // path moves 64 B/clk: a 256x128x64 tile stages 48 KB per 1024 MFMA-cycles per SIMD (47 B/clk, 3/4 of that path),
 // 256x256 31 B/clk, 256x320 28 B/clk. 320 = the UNet's channel quantum (N = 320, 640, 1280, 2560 tile exactly).
-
-typedef __attribute__((address_space(3))) char lds_char_t;
-
-__device__ __attribute__((aligned(16))) uint32_t g_zero_chunk2[8];
-
-__device__ __forceinline__ int lds_off2(int row, int chunk) {
-    return row * 128 + ((chunk ^ ((row >> 1) & 7)) << 4);
-}
-
-// one wave instruction: 64 lanes x 16 B -> LDS [lds_dst, lds_dst + 1024), lane-linear
-__device__ __forceinline__ void glds16(const void* gsrc, unsigned lds_dst_uniform) {
-    unsigned keep;
-    asm volatile(
-        "s_mov_b32 %0, m0\n\t"
-        "s_mov_b32 m0, %2\n\t"
-        "s_nop 0\n\t"
-        "global_load_lds_dwordx4 %1, off\n\t"
-        "s_mov_b32 m0, %0"
-        : "=&s"(keep)
-        : "v"(gsrc), "s"(lds_dst_uniform)
-        : "memory");
-}
-
-template <int N>
-__device__ __forceinline__ void wait_vmcnt() {
-    asm volatile("s_waitcnt vmcnt(%0)" ::"n"(N) : "memory");
-}
 
 // Split-K scheduling of a launch (host side: dc_gemm_conv_glds_try). A launch covers the logical tiles
 // [tile_begin, tile_begin + tile_count); with splits > 1, blockIdx.y selects a K range and the workgroup writes raw
@@ -102,7 +76,7 @@ __global__ __launch_bounds__(GNT) void gemm_conv_glds_kernel(const DcGemmParams 
     const int n0 = tile_n * BNOUT;
 
     const unsigned lds_base = (unsigned)(unsigned long)((lds_char_t*)smem);
-    const bf16_t* const zero_ptr = reinterpret_cast<const bf16_t*>(g_zero_chunk2);
+    const bf16_t* const zero_ptr = reinterpret_cast<const bf16_t*>(g_zero_chunk);
 
     // ---- staging coordinates: wave instruction j covers LDS slots (j*8 + wave)*64 + lane; slot = row*8 + phys chunk
     const int srow = lane >> 3;                       // row inside the 8-row group of this instruction
@@ -211,11 +185,11 @@ __global__ __launch_bounds__(GNT) void gemm_conv_glds_kernel(const DcGemmParams 
                 const bool ok = (a_base[j] >= 0) & (tt >= 0) & (tt < p.T);
                 src = ok ? a_ptr[j] + shift : zero_ptr;
             }
-            glds16(src, sa + (j * 8 + wave) * 1024);
+            lds_dma16_keep_m0(src, sa + (j * 8 + wave) * 1024);
         }
 #pragma unroll
         for (int j = 0; j < B_IT; ++j)
-            if ((j & 3) == part) glds16(b_ptr[j] + k0, sb + (j * 8 + wave) * 1024);
+            if ((j & 3) == part) lds_dma16_keep_m0(b_ptr[j] + k0, sb + (j * 8 + wave) * 1024);
     };
     auto issue_tile = [&](int kt, int stage) __attribute__((always_inline)) {
 #pragma unroll
@@ -270,13 +244,13 @@ __global__ __launch_bounds__(GNT) void gemm_conv_glds_kernel(const DcGemmParams 
             bf16x8_t xf[2], wf[NB];
 #pragma unroll
             for (int mb = 0; mb < 2; ++mb)
-                xf[mb] = *reinterpret_cast<const bf16x8_t*>(sa + lds_off2(wm * 64 + mb * 32 + fr, kk * 2 + fh));
+                xf[mb] = *reinterpret_cast<const bf16x8_t*>(sa + lds_off128(wm * 64 + mb * 32 + fr, kk * 2 + fh));
 #pragma unroll
             for (int nb = 0; nb < NB; ++nb) {
                 int brow;
                 if (GEGLU) brow = (nb < NB / 2 ? 0 : BN / 2) + wn * (BN / 4) + (nb % (NB / 2 > 0 ? NB / 2 : 1)) * 32;
                 else brow = wn * (32 * NB) + nb * 32;
-                wf[nb] = *reinterpret_cast<const bf16x8_t*>(sb + lds_off2(brow + fr, kk * 2 + fh));
+                wf[nb] = *reinterpret_cast<const bf16x8_t*>(sb + lds_off128(brow + fr, kk * 2 + fh));
             }
 #pragma unroll
             for (int mb = 0; mb < 2; ++mb)
@@ -638,7 +612,7 @@ __global__ __launch_bounds__(GNT) void gemm_persist_kernel(const DcGemmParams p,
     const int total = nj * nkr;
 
     const unsigned lds_base = (unsigned)(unsigned long)((lds_char_t*)smem);
-    const bf16_t* const zero_ptr = reinterpret_cast<const bf16_t*>(g_zero_chunk2);
+    const bf16_t* const zero_ptr = reinterpret_cast<const bf16_t*>(g_zero_chunk);
     const int srow = lane >> 3;
     const int pchunk = lane & 7;
 
@@ -727,12 +701,12 @@ __global__ __launch_bounds__(GNT) void gemm_persist_kernel(const DcGemmParams p,
                 const int tt = a_aux[q] + tap - 1;
                 src = (tt >= 0 && tt < p.T) ? a_ptr[q] + shift : zero_ptr;
             }
-            glds16(src, sa + (q * 8 + wave) * 1024);
+            lds_dma16_keep_m0(src, sa + (q * 8 + wave) * 1024);
         }
         if (!res_tile) {
 #pragma unroll
             for (int q = 0; q < B_IT; ++q)
-                if ((q & 3) == part) glds16(b_ptr[q] + k0, sb + (q * 8 + wave) * 1024);
+                if ((q & 3) == part) lds_dma16_keep_m0(b_ptr[q] + k0, sb + (q * 8 + wave) * 1024);
         }
         if (part == 3) {
             if (++i_stage >= GSTAGES) i_stage = 0;
@@ -789,13 +763,13 @@ __global__ __launch_bounds__(GNT) void gemm_persist_kernel(const DcGemmParams p,
                 bf16x8_t xf[2], wf[NB];
 #pragma unroll
                 for (int mb = 0; mb < 2; ++mb)
-                    xf[mb] = *reinterpret_cast<const bf16x8_t*>(sa + lds_off2(wm * 64 + mb * 32 + fr, kk * 2 + fh));
+                    xf[mb] = *reinterpret_cast<const bf16x8_t*>(sa + lds_off128(wm * 64 + mb * 32 + fr, kk * 2 + fh));
 #pragma unroll
                 for (int nb = 0; nb < NB; ++nb) {
                     int brow;
                     if (GEGLU) brow = (nb < NBX ? 0 : BN / 2) + wn * (BN / 4) + (nb % NBX) * 32;
                     else brow = wn * (32 * NB) + nb * 32;
-                    wf[nb] = *reinterpret_cast<const bf16x8_t*>(sb + lds_off2(brow + fr, kk * 2 + fh));
+                    wf[nb] = *reinterpret_cast<const bf16x8_t*>(sb + lds_off128(brow + fr, kk * 2 + fh));
                 }
 #pragma unroll
                 for (int mb = 0; mb < 2; ++mb)
@@ -838,7 +812,7 @@ __global__ __launch_bounds__(GNT) void gemm_persist_kernel(const DcGemmParams p,
 #pragma unroll
                         for (int mb = 0; mb < 2; ++mb) {
                             const bf16x8_t xr = *reinterpret_cast<const bf16x8_t*>(
-                                sr + lds_off2(wm * 64 + mb * 32 + fr_r, (wn * 2 + i) * 2 + fh_r));
+                                sr + lds_off128(wm * 64 + mb * 32 + fr_r, (wn * 2 + i) * 2 + fh_r));
                             acc[mb][j] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(idf, xr, acc[mb][j], 0, 0, 0);
                         }
                     }

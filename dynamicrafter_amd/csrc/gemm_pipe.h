@@ -1,6 +1,6 @@
 // Shared preamble of the one-wave-per-SIMD 256 x 320 x 64 GEMM / implicit-GEMM conv kernel (gemm_pipe16.h; included by
-// gemm_conv_glds.hip inside its namespace: shares GemmSplit, splitk_reduce_kernel and persist_epilogue): ring geometry, the
-// bounded counter wait, the unrolling helper and the activation load macro. (The kernel's first form, on
+// gemm_conv_glds.hip inside its namespace: shares GemmSplit, splitk_reduce_kernel and persist_epilogue): ring geometry and the
+// activation load macro (the bounded counter wait and the unrolling helper are lds_stage.h's). (The kernel's first form, on
 // v_mfma_f32_32x32x16_bf16, lost to the 16x16x32 form on every shape - DESIGN 3.4 - and lives in tools/experimental/gemm_pipe32.h.)
 // The design, as it stands in gemm_pipe16.h:
 //
@@ -33,8 +33,6 @@ constexpr int GP_CNT = GP_RING + 4 * 2048;        // behind the four epilogue pa
 constexpr int GP_LDS = GP_CNT + 64;
 
 typedef __attribute__((ext_vector_type(4))) int gp_i32x4_t;
-typedef const volatile __attribute__((address_space(3))) bf16x8_t gp_lds_frag_t;
-typedef __attribute__((address_space(3))) int gp_lds_int_t;
 
 #ifdef GP_STAMPS    // tool build (tools/pipe_stamps.py): shader clocks a wave spends at its four waiting points, summed over the K loop
 #define GP_ST_BEGIN() const unsigned long long st_t0__ = __builtin_readcyclecounter()
@@ -43,19 +41,6 @@ typedef __attribute__((address_space(3))) int gp_lds_int_t;
 #define GP_ST_BEGIN() do { } while (0)
 #define GP_ST_END(i) do { } while (0)
 #endif
-// A wait on an LDS counter. Every wave posts every counter the same number of times, so a wait always ends; the bound (about
-// 10 ms, once per wave) only keeps a future bookkeeping mistake from hanging the GPU. A wave that gave up carries on with
-// whatever the ring holds - its tile is garbage - and ORs DC_ERRW_GEMM_PIPE into the library's error word (GemmSplit::err)
-// before it leaves: dc_error_word_read / ops.check_error_word make that loud on the host.
-#define GP_SPIN(cond, reread)                                              \
-    do {                                                                   \
-        int spins__ = 0;                                                   \
-        while (!gave_up && (cond)) { reread; if (++spins__ > 200000) gave_up = 1; } \
-    } while (0)
-
-template <int V> using gp_ic = std::integral_constant<int, V>;
-template <int... G, class F>
-__device__ __forceinline__ void gp_for(std::integer_sequence<int, G...>, F&& f) { (f(gp_ic<G>{}), ...); }
 
 #define GP_LOAD_A_(dst, vo, rs, so, IMM) \
     asm volatile("buffer_load_dwordx4 %0, %1, %2, %3 offen offset:" IMM : "=&v"(dst) : "v"(vo), "s"(rs), "s"(so))

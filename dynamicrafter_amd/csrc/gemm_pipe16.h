@@ -57,11 +57,11 @@ void gemm_pipe320x16_kernel(const DcGemmParams p, const GemmSplit sp) {
     const int kt_hi = (int)(((long long)(by + 1) * nk_all) / nsplit);
     const int nk = kt_hi - kt_lo;
 
-    gp_lds_int_t* const cnt_landed = (gp_lds_int_t*)(smem + GP_CNT);
-    gp_lds_int_t* const cnt_freed = cnt_landed + 1;
+    lds_int_t* const cnt_landed = (lds_int_t*)(smem + GP_CNT);
+    lds_int_t* const cnt_freed = cnt_landed + 1;
     if (tid < 2) cnt_landed[tid] = 0;
     __syncthreads();
-    int gave_up = 0;                                        // see GP_SPIN
+    int gave_up = 0;                                        // see LDS_SPIN (lds_stage.h)
 
     // ---- activation rows: lane (lr, lq) holds bytes [64 s + 16 lq, +16) of the K tile's slice of rows 16 rb + lr of its wave
     const unsigned lda2 = (unsigned)p.lda * 2u;
@@ -170,7 +170,7 @@ void gemm_pipe320x16_kernel(const DcGemmParams p, const GemmSplit sp) {
     };
 
     // ---- weight tile by LDS-DMA: exactly as in gemm_pipe.h
-    const unsigned lds_base = (unsigned)(uintptr_t)((const __attribute__((address_space(3))) char*)smem);
+    const unsigned lds_base = (unsigned)(uintptr_t)((const lds_char_t*)smem);
     unsigned voffB[10];
 #pragma unroll
     for (int j = 0; j < 10; ++j) {
@@ -180,9 +180,6 @@ void gemm_pipe320x16_kernel(const DcGemmParams p, const GemmSplit sp) {
     }
     auto w_src = [&](int kt) __attribute__((always_inline)) -> unsigned long long {
         return (unsigned long long)(uintptr_t)p.W + ((unsigned long long)n0 * p.K + (unsigned long long)kt * 64) * 2ull;
-    };
-    auto dma = [&](unsigned lds_dst, unsigned voff, unsigned long long sbase) __attribute__((always_inline)) {
-        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_dst), "v"(voff), "s"(sbase) : "memory");
     };
 
     // ---- fragment reads: weight fragment (s, cb) = rows 16 cb + lr, 16-byte chunk 4 s + lq
@@ -196,7 +193,7 @@ void gemm_pipe320x16_kernel(const DcGemmParams p, const GemmSplit sp) {
         }
     bf16x8_t Bf[5];
     auto rd_b = [&](int slot, unsigned addr, int cb) __attribute__((always_inline)) {
-        Bf[slot] = *(gp_lds_frag_t*)((const __attribute__((address_space(3))) char*)(uintptr_t)addr + cb * 2048);
+        Bf[slot] = *(lds_vfrag_t*)((const lds_char_t*)(uintptr_t)addr + cb * 2048);
     };
 
     u32x4_t A[3][4][2];
@@ -214,7 +211,7 @@ void gemm_pipe320x16_kernel(const DcGemmParams p, const GemmSplit sp) {
     for (int t = 0; t < 2; ++t) {
         const unsigned long long ws = w_src(clampk(t));
 #pragma unroll
-        for (int j = 0; j < 10; ++j) dma(lds_base + t * GP_STAGE + (j * 4 + wave) * 1024, voffB[j], ws);
+        for (int j = 0; j < 10; ++j) lds_dma16_sbase(lds_base + t * GP_STAGE + (j * 4 + wave) * 1024, voffB[j], ws);
         unsigned vo[4];
         int soff;
         a_tile(clampk(t), vo, soff);
@@ -227,8 +224,8 @@ void gemm_pipe320x16_kernel(const DcGemmParams p, const GemmSplit sp) {
     wait_vmcnt<26>();                                       // this wave's pieces of tile 0 are in LDS
     if (lane == 0) __hip_atomic_fetch_add(cnt_landed, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     {
-        int seen = *(volatile gp_lds_int_t*)cnt_landed;
-        GP_SPIN(__builtin_amdgcn_readfirstlane(seen) < 4, seen = *(volatile gp_lds_int_t*)cnt_landed);
+        int seen = *(volatile lds_int_t*)cnt_landed;
+        LDS_SPIN(__builtin_amdgcn_readfirstlane(seen) < 4, seen = *(volatile lds_int_t*)cnt_landed);
         asm volatile("" ::: "memory");
     }
 #pragma unroll
@@ -245,7 +242,7 @@ void gemm_pipe320x16_kernel(const DcGemmParams p, const GemmSplit sp) {
         gp_f32x4_t (&acc1)[4][20] = acc;
         bf16x8_t (&Bf1)[5] = Bf;
         u32x4_t (&A1)[3][4][2] = A;
-        gp_for(std::make_integer_sequence<int, 160>{}, [&](auto G_) __attribute__((always_inline)) {
+        for_ic(std::make_integer_sequence<int, 160>{}, [&](auto G_) __attribute__((always_inline)) {
             constexpr int g = decltype(G_)::value;
             gp_f32x4_t (&acc_)[4][20] = acc1;
             bf16x8_t (&Bf_)[5] = Bf1;
@@ -261,16 +258,16 @@ void gemm_pipe320x16_kernel(const DcGemmParams p, const GemmSplit sp) {
                 if constexpr (F < 40) rd_b(F % 5, bofs[ST][F / 20], F % 20);
                 else rd_b(F % 5, bofs[ST1][0], F - 40);
             } else if constexpr ((g & 3) == 2) {
-                if constexpr (g == 2) seen_f = *(volatile gp_lds_int_t*)cnt_freed;
+                if constexpr (g == 2) seen_f = *(volatile lds_int_t*)cnt_freed;
                 if constexpr (g == 6) {
                     // stage ST2 held tile t-1: every wave is past its last fragment of it
-                    GP_SPIN(__builtin_amdgcn_readfirstlane(seen_f) < 4 * t, seen_f = *(volatile gp_lds_int_t*)cnt_freed);
+                    LDS_SPIN(__builtin_amdgcn_readfirstlane(seen_f) < 4 * t, seen_f = *(volatile lds_int_t*)cnt_freed);
                     asm volatile("" ::: "memory");
                     ws = w_src(kt2);
                 }
                 if constexpr (g >= 10 && g <= 82 && ((g - 10) & 7) == 0) {
                     constexpr int j = (g - 10) >> 3;
-                    dma(lds_base + ST2 * GP_STAGE + (j * 4 + wave) * 1024, voffB[j], ws);
+                    lds_dma16_sbase(lds_base + ST2 * GP_STAGE + (j * 4 + wave) * 1024, voffB[j], ws);
                 }
                 if constexpr (g == 86) {
                     wait_vmcnt<18>();                       // this wave's pieces of tile t+1 (issued a tile ago) are in LDS
@@ -287,10 +284,10 @@ void gemm_pipe320x16_kernel(const DcGemmParams p, const GemmSplit sp) {
                     if constexpr ((i >> 2) == 0) GP_LOAD_A_(A_[ST2][i & 3][0], vo[i & 3], ars, soff, "0");
                     else GP_LOAD_A_(A_[ST2][i & 3][1], vo[i & 3], ars, soff, "64");
                 }
-                if constexpr (g == 118) seen_l = *(volatile gp_lds_int_t*)cnt_landed;
+                if constexpr (g == 118) seen_l = *(volatile lds_int_t*)cnt_landed;
                 if constexpr (g == 142) {
                     // all four shares of tile t+1 have landed (it is first read two gaps on)
-                    GP_SPIN(t + 1 < nk && __builtin_amdgcn_readfirstlane(seen_l) < 4 * (t + 2), seen_l = *(volatile gp_lds_int_t*)cnt_landed);
+                    LDS_SPIN(t + 1 < nk && __builtin_amdgcn_readfirstlane(seen_l) < 4 * (t + 2), seen_l = *(volatile lds_int_t*)cnt_landed);
                     asm volatile("" ::: "memory");
                 }
                 if constexpr (g == 150) {
@@ -307,11 +304,11 @@ void gemm_pipe320x16_kernel(const DcGemmParams p, const GemmSplit sp) {
     const unsigned long long st_real0 = __builtin_amdgcn_s_memrealtime();
 #endif
     for (int t = 0; t < nk; t += 3) {
-        tile(gp_ic<0>{}, t);
+        tile(ic<0>{}, t);
         if (t + 1 >= nk) break;
-        tile(gp_ic<1>{}, t + 1);
+        tile(ic<1>{}, t + 1);
         if (t + 2 >= nk) break;
-        tile(gp_ic<2>{}, t + 2);
+        tile(ic<2>{}, t + 2);
     }
     wait_vmcnt<0>();
     gp16_settle(acc);

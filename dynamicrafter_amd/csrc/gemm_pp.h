@@ -72,15 +72,15 @@ void gemm_pp_kernel(const DcGemmParams p, const GemmSplit sp, const int tile_gro
     const int n0 = tile_n * BNOUT;
     const int nk = p.K / PP_K;
 
-    gp_lds_int_t* const cnt_landed = (gp_lds_int_t*)(smem + PP_CNT);
-    gp_lds_int_t* const cnt_freed = cnt_landed + 1;
+    lds_int_t* const cnt_landed = (lds_int_t*)(smem + PP_CNT);
+    lds_int_t* const cnt_freed = cnt_landed + 1;
     if (tid < 2) cnt_landed[tid] = 0;
     __syncthreads();
-    int gave_up = 0;                                        // see GP_SPIN (gemm_pipe.h)
+    int gave_up = 0;                                        // see LDS_SPIN (lds_stage.h)
 
     // ---- LDS-DMA pieces (1 KB, lane-linear in LDS = 16 rows x 64 B): lane l carries row l >> 2 of the piece, chunk slot l & 3,
     // which holds source chunk (l & 3) ^ ((row >> 1) & 3) = (l & 3) ^ ((l >> 3) & 3) (a piece starts at a multiple of 16 rows)
-    const unsigned lds_base = (unsigned)(uintptr_t)((const __attribute__((address_space(3))) char*)smem);
+    const unsigned lds_base = (unsigned)(uintptr_t)((const lds_char_t*)smem);
     const unsigned src_chunk = (unsigned)(((lane & 3) ^ ((lane >> 3) & 3)) << 4);
     unsigned voffA[4], voffW[2];
 #pragma unroll
@@ -104,9 +104,6 @@ void gemm_pp_kernel(const DcGemmParams p, const GemmSplit sp, const int tile_gro
         asm volatile("" : "+v"(voffW[j]));
     }
     const unsigned long long a_base = (unsigned long long)(uintptr_t)p.A, w_base = (unsigned long long)(uintptr_t)p.W;
-    auto dma = [&](unsigned lds_dst, unsigned voff, unsigned long long sbase) __attribute__((always_inline)) {
-        asm volatile("s_mov_b32 m0, %0\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, %2" ::"s"(lds_dst), "v"(voff), "s"(sbase) : "memory");
-    };
     const unsigned a_dst = lds_base + wave * 4096;          // + stage * PP_ASTAGE + j * 1024
     const unsigned w_dst = lds_base + PP_WBASE + wave * 2048;      // + stage * PP_WSTAGE + j * 1024
 
@@ -117,7 +114,7 @@ void gemm_pp_kernel(const DcGemmParams p, const GemmSplit sp, const int tile_gro
     bf16x8_t Wf[4];        // ring of 4, read 3 fragments (12 MFMAs) ahead
     bf16x8_t Af[2][4];     // the 4 row blocks of a tile; the other set receives the next tile's
     auto rd = [&](bf16x8_t& dst, unsigned addr, int imm) __attribute__((always_inline)) {
-        dst = *(gp_lds_frag_t*)((const __attribute__((address_space(3))) char*)(uintptr_t)addr + imm);
+        dst = *(lds_vfrag_t*)((const lds_char_t*)(uintptr_t)addr + imm);
     };
 
     gp_f32x4_t acc[4][8];
@@ -133,15 +130,15 @@ void gemm_pp_kernel(const DcGemmParams p, const GemmSplit sp, const int tile_gro
     for (int t = 0; t < 2; ++t) {
         const unsigned long long as = a_base + (unsigned long long)t * 64ull, ws = w_base + (unsigned long long)t * 64ull;
 #pragma unroll
-        for (int j = 0; j < 4; ++j) dma(a_dst + t * PP_ASTAGE + j * 1024, voffA[j], as);
+        for (int j = 0; j < 4; ++j) lds_dma16_sbase(a_dst + t * PP_ASTAGE + j * 1024, voffA[j], as);
 #pragma unroll
-        for (int j = 0; j < 2; ++j) dma(w_dst + t * PP_WSTAGE + j * 1024, voffW[j], ws);
+        for (int j = 0; j < 2; ++j) lds_dma16_sbase(w_dst + t * PP_WSTAGE + j * 1024, voffW[j], ws);
     }
     wait_vmcnt<6>();                                        // this wave's pieces of tile 0
     if (lane == 0) __hip_atomic_fetch_add(cnt_landed, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
     {
-        int seen = *(volatile gp_lds_int_t*)cnt_landed;
-        GP_SPIN(__builtin_amdgcn_readfirstlane(seen) < 4, seen = *(volatile gp_lds_int_t*)cnt_landed);
+        int seen = *(volatile lds_int_t*)cnt_landed;
+        LDS_SPIN(__builtin_amdgcn_readfirstlane(seen) < 4, seen = *(volatile lds_int_t*)cnt_landed);
         asm volatile("" ::: "memory");
     }
 #pragma unroll
@@ -176,7 +173,7 @@ void gemm_pp_kernel(const DcGemmParams p, const GemmSplit sp, const int tile_gro
         bf16x8_t (&Af1)[2][4] = Af;
         unsigned (&va1)[4] = va;
         unsigned (&vw1)[2] = vw;
-        gp_for(std::make_integer_sequence<int, 32>{}, [&](auto G_) __attribute__((always_inline)) {
+        for_ic(std::make_integer_sequence<int, 32>{}, [&](auto G_) __attribute__((always_inline)) {
             constexpr int g = decltype(G_)::value;
             gp_f32x4_t (&acc_)[4][8] = acc1;
             bf16x8_t (&Wf_)[4] = Wf1;
@@ -190,18 +187,18 @@ void gemm_pp_kernel(const DcGemmParams p, const GemmSplit sp, const int tile_gro
                 if constexpr (F < 8) rd(Wf_[F % 4], wofs, ST * PP_WSTAGE + F * 1024);
                 else rd(Wf_[F % 4], wofs, ST1 * PP_WSTAGE + (F - 8) * 1024);
             }
-            if constexpr (g == 1) seen_f = *(volatile gp_lds_int_t*)cnt_freed;
+            if constexpr (g == 1) seen_f = *(volatile lds_int_t*)cnt_freed;
             // this wave's activation rows of tile t + 2: its own region of stage ST2, which it finished reading in tile t - 2
             if constexpr (g == 2 || g == 3 || g == 5 || g == 6) {
                 constexpr int j = g < 4 ? g - 2 : g - 3;
-                dma(a_dst + ST2 * PP_ASTAGE + j * 1024, va_[j], a_base + koff);
+                lds_dma16_sbase(a_dst + ST2 * PP_ASTAGE + j * 1024, va_[j], a_base + koff);
             }
             if constexpr (g == 7) {
                 // weight stage ST2 held tile t - 1: every wave is past its last fragment of it
-                GP_SPIN(__builtin_amdgcn_readfirstlane(seen_f) < 4 * t, seen_f = *(volatile gp_lds_int_t*)cnt_freed);
+                LDS_SPIN(__builtin_amdgcn_readfirstlane(seen_f) < 4 * t, seen_f = *(volatile lds_int_t*)cnt_freed);
                 asm volatile("" ::: "memory");
             }
-            if constexpr (g == 9 || g == 10) dma(w_dst + ST2 * PP_WSTAGE + (g - 9) * 1024, vw_[g - 9], w_base + koff);
+            if constexpr (g == 9 || g == 10) lds_dma16_sbase(w_dst + ST2 * PP_WSTAGE + (g - 9) * 1024, vw_[g - 9], w_base + koff);
             if constexpr (g == 11) {
                 wait_vmcnt<6>();                            // everything but this tile's 6 pieces: the pieces of tile t + 1 are in LDS
                 if (lane == 0) __hip_atomic_fetch_add(cnt_landed, 1, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_WORKGROUP);
@@ -210,10 +207,10 @@ void gemm_pp_kernel(const DcGemmParams p, const GemmSplit sp, const int tile_gro
                 constexpr int rb = g < 16 ? g - 13 : g - 15;
                 rd(Af_[AB ^ 1][rb], aofs, ST1 * PP_ASTAGE + rb * 1024);
             }
-            if constexpr (g == 15) seen_l = *(volatile gp_lds_int_t*)cnt_landed;
+            if constexpr (g == 15) seen_l = *(volatile lds_int_t*)cnt_landed;
             if constexpr (g == 19) {
                 // all four shares of weight tile t + 1 have landed (it is first read at gap 20)
-                GP_SPIN(more1 && __builtin_amdgcn_readfirstlane(seen_l) < 4 * (t + 2), seen_l = *(volatile gp_lds_int_t*)cnt_landed);
+                LDS_SPIN(more1 && __builtin_amdgcn_readfirstlane(seen_l) < 4 * (t + 2), seen_l = *(volatile lds_int_t*)cnt_landed);
                 asm volatile("" ::: "memory");
             }
             if constexpr (g == 21) {
@@ -225,17 +222,17 @@ void gemm_pp_kernel(const DcGemmParams p, const GemmSplit sp, const int tile_gro
         });
     };
     for (int t = 0; t < nk; t += 6) {
-        tile(gp_ic<0>{}, gp_ic<0>{}, t);
+        tile(ic<0>{}, ic<0>{}, t);
         if (t + 1 >= nk) break;
-        tile(gp_ic<1>{}, gp_ic<1>{}, t + 1);
+        tile(ic<1>{}, ic<1>{}, t + 1);
         if (t + 2 >= nk) break;
-        tile(gp_ic<2>{}, gp_ic<0>{}, t + 2);
+        tile(ic<2>{}, ic<0>{}, t + 2);
         if (t + 3 >= nk) break;
-        tile(gp_ic<0>{}, gp_ic<1>{}, t + 3);
+        tile(ic<0>{}, ic<1>{}, t + 3);
         if (t + 4 >= nk) break;
-        tile(gp_ic<1>{}, gp_ic<0>{}, t + 4);
+        tile(ic<1>{}, ic<0>{}, t + 4);
         if (t + 5 >= nk) break;
-        tile(gp_ic<2>{}, gp_ic<1>{}, t + 5);
+        tile(ic<2>{}, ic<1>{}, t + 5);
     }
     wait_vmcnt<0>();
     pp_settle(acc);
