@@ -1,8 +1,8 @@
 // Kernels that keep the activation rows of a workgroup in REGISTERS as MFMA operand fragments ("X-stationary") and stream
 // only weights through LDS - the UNet's level-0 / level-1 row-wise operator chains, fused:
-//   ff_geglu_fused320_kernel   x = x + ff2(geglu(ff1(norm3(x))))  [+ the transformer's proj_out and residual]      dim 320
+//   ff_geglu_fused320_kernel   x = x + ff2(geglu(ff1(norm3(x))))  [+ the transformer's proj_out and residual]            dim 320
 //   norm_linear_kernel         Linear(LayerNorm(x)) / Linear(GroupNorm(x)) / Linear(x)                         K 320 / 640
-//   ln_qkv_tattn320_kernel     LayerNorm + to_q/k/v + attention over the 16 frames of a position               dim 320
+//   ln_qkv_tattn_kernel        LayerNorm + to_q/k/v + attention over the 16 frames of a position         dim 320 / 640
 //   gn_silu_tconv_kernel       GroupNorm + SiLU + Conv3d (3,1,1) (+ identity) of a TemporalConvBlock            C 320 / 640
 // Common technique: volatile LDS fragment loads + empty `asm volatile` anchors pin the LDS prefetch distance and the
 // MFMA / VALU interleave (hipcc otherwise sinks every LDS read to just in front of its use); LDS-DMA pieces addressed by a
@@ -68,6 +68,166 @@ __device__ unsigned long long g_ff_stamps[8];
 #else
 #define FF_GELU(x) gelu_phi_f(x)      // the last chunk's stand-alone GEGLU: the same function as the interleaved stream
 #endif
+
+// ---------------------------------------------------------------------------------------------------------------------
+// The X-stationary core: what the four kernels below share. Lane (fr, fh) = (lane & 31, lane >> 5) of a wave holds, for
+// row fr of the wave's 32 rows, the k elements 16 kk + 8 fh .. + 7 of X fragment kk (the MFMA's B operand). A weight
+// STAGE is 32 output channels x 320 k = 5 K tiles of [32 rows][128 B], lds_off128-swizzled (20 KB): 20 LDS-DMA pieces of
+// 8 rows x 128 B, 5 per wave, and 20 MFMAs 32x32x16 per wave. A chunk's 32 x 32 result leaves through a wave-private patch
+// of 32 rows x 64 B: written in accumulator layout (8-byte slots), read back row-major (16 bytes per lane, 16 rows x 64 B
+// per store instruction).
+constexpr int LCH = 32;                        // output channels per chunk
+constexpr int LW_STAGE = LCH * FD * 2;         // 20 KB
+
+// Per-lane source offsets of a wave's 5 pieces, computed once per kernel: piece u = wave * 5 + i is (K tile t, 8-row group
+// g) and lands at LDS offset u * 1024 of its stage. ROW_BYTES: a weight row in memory, TILE_BYTES: from one K tile to the
+// next. PIN: opaque to hipcc, or it re-derives the wave-uniform parts at every use (5 scalar instructions per piece).
+template <int ROW_BYTES, int TILE_BYTES, bool PIN = true>
+__device__ __forceinline__ void xs_piece_offsets(unsigned (&vo)[5], int wave, int lane) {
+#pragma unroll
+    for (int i = 0; i < 5; ++i) {
+        const int u = wave * 5 + i;                      // (K tile t, 8-row group g): LDS offset u * 1024
+        const int t = u >> 2, g = u & 3;
+        vo[i] = (unsigned)((g * 8 + (lane >> 3)) * ROW_BYTES + t * TILE_BYTES + (((lane & 7) ^ ((g * 4 + (lane >> 4)) & 7)) << 4));
+        if constexpr (PIN) asm volatile("" : "+v"(vo[i]));
+    }
+}
+// LDS address of piece i of this wave in the stage at byte offset `stage_off`
+__device__ __forceinline__ unsigned xs_stage_dst(unsigned lds_base, int stage_off, int wave, int i) {
+    return lds_base + stage_off + (wave * 5 + i) * 1024;
+}
+// all 5 pieces of a stage at once (the stages in flight before the first MFMA)
+__device__ __forceinline__ void xs_issue_stage(unsigned lds_base, int stage_off, int wave, const unsigned (&vo)[5], uint64_t sbase) {
+#pragma unroll
+    for (int i = 0; i < 5; ++i) lds_dma16_sbase(xs_stage_dst(lds_base, stage_off, wave, i), vo[i], sbase);
+}
+
+// pinned read of the weight fragment (row, k step kk) of a stage whose K tiles hold ROWS rows
+template <int ROWS = 32>
+__device__ __forceinline__ bf16x8_t xs_read_frag(const char* stage, int kk, int row, int fh) {
+    return *(lds_vfrag_t*)((lds_char_t*)stage + (kk >> 2) * (ROWS * 128) + lds_off128(row, (kk & 3) * 2 + fh));
+}
+
+// One stage: acc += W_stage X^T for the 20 X fragments xf[k0 .. k0 + 19]. The fragments are read PD k steps ahead of the
+// MFMA that consumes them through volatile loads, every consumer passes through an empty volatile asm (the PD / PD2 comment
+// in ff_geglu_fused320_kernel tells why), and issue(i), i = 0 .. 4 - the caller's "piece i of the next stage" - goes out
+// behind each of the first five MFMAs, which work the ~60 cycles of a piece off in the matrix pipe.
+template <int PD, int NK, class Issue>
+__device__ __forceinline__ void xs_stage_mma(const char* stage, const bf16x8_t (&xf)[NK], int k0, f32x16_t& acc, int fr, int fh,
+                                             Issue&& issue) {
+    bf16x8_t wr[PD];
+#pragma unroll
+    for (int kk = 0; kk < PD; ++kk) wr[kk] = xs_read_frag(stage, kk, fr, fh);
+#pragma unroll
+    for (int kk = 0; kk < FD / 16; ++kk) {
+        bf16x8_t f = wr[kk % PD];
+        if (kk + PD < FD / 16) wr[kk % PD] = xs_read_frag(stage, kk + PD, fr, fh);
+        asm volatile("" : "+v"(f));
+        acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f, xf[k0 + kk], acc, 0, 0, 0);
+        if (kk < 5) issue(kk);
+    }
+}
+
+// How wave row r (0 .. 31) maps to a tensor row: consecutive rows with a bound (ok: inside the tensor; clamped: the last row
+// instead of one past the end, for loads whose result is dropped), or gathered - the wave owns 2 positions x 16 frames of
+// clip b, the frames of a position are HW rows apart.
+struct XsRowsLinear {
+    int m0, M;
+    __device__ __forceinline__ bool ok(int r) const { return m0 + r < M; }
+    __device__ __forceinline__ size_t operator()(int r) const { return (size_t)(m0 + r); }
+    __device__ __forceinline__ size_t clamped(int r) const { int m = m0 + r; if (m >= M) m = M - 1; return (size_t)m; }
+};
+struct XsRowsGather {
+    int b, HW, p0;
+    __device__ __forceinline__ bool ok(int) const { return true; }
+    __device__ __forceinline__ size_t operator()(int r) const { return ((size_t)(b * 16 + (r & 15))) * HW + p0 + (r >> 4); }
+    __device__ __forceinline__ size_t clamped(int r) const { return (*this)(r); }
+};
+
+// X fragments of a row (B operand: lane (row fr, half fh) holds k = 16 kk + 8 fh .. + 7); xrow points at the row's element 8 fh
+template <int NK>
+__device__ __forceinline__ void xs_load_rows(bf16x8_t (&xf)[NK], const bf16_t* xrow) {
+#pragma unroll
+    for (int kk = 0; kk < NK; ++kk) xf[kk] = *reinterpret_cast<const bf16x8_t*>(xrow + kk * 16);
+}
+
+// gamma / beta of a LayerNorm -> lns[0 .. KD), lns[KD .. 2 KD)
+__device__ __forceinline__ void xs_stage_ln_affine(float* lns, int KD, const float* g, const float* b, int tid) {
+    for (int i = tid; i < KD; i += 256) { lns[i] = g[i]; lns[KD + i] = b[i]; }
+}
+// GroupNorm with known statistics of ONE instance (stats: its `groups` (mean, rstd) pairs) as x * a[c] + b[c]:
+// a = gamma rstd, b = beta - mean a
+__device__ __forceinline__ void xs_stage_gn_affine(float* lns, int KD, const float* g, const float* b, const float2* stats, int groups,
+                                                   int tid) {
+    for (int i = tid; i < KD; i += 256) {
+        const float2 st = stats[i / (KD / groups)];
+        const float a = g[i] * st.y;
+        lns[i] = a; lns[KD + i] = b[i] - st.x * a;
+    }
+}
+// the bias in LDS: as global loads in the chunk epilogue they were two exposed round trips per 20 MFMAs
+__device__ __forceinline__ void xs_stage_bias(float* bls, const float* bias, int N, int tid) {
+    for (int i = tid; i < N; i += 256) bls[i] = bias[i];
+}
+
+// The chunk epilogue is + bias (+ residual), bf16 pack, into the patch, row-major 16-byte read-back, store. What follows is
+// its vocabulary; the sequence itself stays in each kernel: as ONE function (or lambda) it came out of hipcc with the last
+// MFMAs of the stage loop and the first LDS waits of the epilogue in another order, and with other register counts, in every
+// kernel that used it (profiles/xs_core_isa.txt). Two residual styles, kept apart because they round differently:
+//   fp32: the residual rows (xs_load_chunk_rows, requested a chunk's MFMAs ahead) go through the patch the other way round -
+//         row-major in, accumulator layout out (xs_add_bf16x4 onto the bias) - the sum is formed in fp32 and rounded to bf16
+//         once, as the tile GEMM's residual epilogue does (one wave's LDS operations execute in order: no barrier);
+//   bf16: the rows are added to the packed rows after read-back (xs_add_bf16x8): bf16 where the stand-alone path rounds
+//         (result + bias, then + residual).
+// The patch: the 8-byte slot of accumulator values 4 q .. 4 q + 3 of lane (fr, fh) (channels 8 q + 4 fh .. + 3 of row fr), and
+// the 16-byte piece rc (channels 8 rc .. + 7) of row r
+__device__ __forceinline__ uint2* xs_patch_acc(char* ebuf, int fr, int fh, int q) {
+    return reinterpret_cast<uint2*>(ebuf + fr * 64 + (((2 * q + fh) ^ (((fr >> 1) & 3) << 1)) << 3));
+}
+__device__ __forceinline__ u32x4_t* xs_patch_row(char* ebuf, int r, int rc) {
+    return reinterpret_cast<u32x4_t*>(ebuf + r * 64 + ((rc ^ ((r >> 1) & 3)) << 4));
+}
+// this lane's two 16-byte pieces (rows lane >> 2 and + 16, channels n0 + 8 (lane & 3) .. + 7) of a chunk of a row-major tensor,
+// in the coalesced pattern of the stores (16 rows x 64 B per instruction)
+template <class Rows>
+__device__ __forceinline__ void xs_load_chunk_rows(u32x4_t (&d)[2], const bf16_t* R, int ldr, const Rows& rows, int n0, int lane) {
+#pragma unroll
+    for (int t = 0; t < 2; ++t)
+        d[t] = *reinterpret_cast<const u32x4_t*>(R + rows.clamped(t * 16 + (lane >> 2)) * ldr + n0 + (lane & 3) * 8);
+}
+__device__ __forceinline__ void xs_add_bf16x8(u32x4_t& d, const u32x4_t& rr) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e)
+        d[e] = pack_bf2(__uint_as_float(d[e] << 16) + __uint_as_float(rr[e] << 16),
+                        __uint_as_float(d[e] & 0xffff0000u) + __uint_as_float(rr[e] & 0xffff0000u));
+}
+__device__ __forceinline__ void xs_add_bf16x4(float4& bv, uint2 rv) {
+    bv.x += __uint_as_float(rv.x << 16); bv.y += __uint_as_float(rv.x & 0xffff0000u);
+    bv.z += __uint_as_float(rv.y << 16); bv.w += __uint_as_float(rv.y & 0xffff0000u);
+}
+// accumulator values 4 q .. 4 q + 3 + bv, packed to bf16
+__device__ __forceinline__ uint2 xs_pack_acc(const f32x16_t& acc, int q, const float4& bv) {
+    uint2 pk;
+    pk.x = pack_bf2(acc[4 * q] + bv.x, acc[4 * q + 1] + bv.y);
+    pk.y = pack_bf2(acc[4 * q + 2] + bv.z, acc[4 * q + 3] + bv.w);
+    return pk;
+}
+
+// A launch with few row tiles splits N over nsplit workgroups per tile (xs_split_n), `part` of them taking the chunks
+// [c_begin, c_end). The nsplit workgroups of a row tile read the same activation rows: they are 8 block ids apart, i.e. on
+// one XCD at about the same time, so that the second read is an L2 hit (consecutive ids go to different XCDs: counters showed
+// X fetched nsplit times). The grid is padded to groups of 8 tiles x nsplit: the caller drops tiles past its last one.
+struct XsPart { int tile, c_begin, c_end; };
+__device__ __forceinline__ XsPart xs_part_decode(int nsplit, int cpp, int nch) {
+    const int bgrp = (int)blockIdx.x / (8 * nsplit), brem = (int)blockIdx.x - bgrp * (8 * nsplit);
+    const int part = brem >> 3;
+    XsPart s;
+    s.tile = bgrp * 8 + (brem & 7);
+    s.c_begin = part * cpp;
+    s.c_end = s.c_begin + cpp;
+    if (s.c_end > nch) s.c_end = nch;
+    return s;
+}
 
 // LayerNorm of the rows held as X fragments (lanes (fr, 0) and (fr, 1) hold the two halves of row fr), two-pass in
 // registers (BasicTransformerBlock norm1/2/3, lvdm/modules/attention.py:225-227, eps 1e-5); the result is rounded to bf16
@@ -222,15 +382,10 @@ void ff_geglu_fused320_kernel(const FfParams p) {
     for (int tile = blockIdx.x; tile < tiles; tile += gridDim.x) {
         const int m0 = tile * FBM + wave * 32;
         // ---- X fragments of this wave's 32 rows (B operand: lane (row fr, half fh) holds k = 16 kk + 8 fh .. + 7)
+        const XsRowsLinear rows{m0, p.M};
         bf16x8_t xf[FD / 16];
-        {
-            int mr = m0 + fr;
-            if (mr >= p.M) mr = p.M - 1;
-            const bf16_t* xr = p.X + (size_t)mr * p.ldx + fh * 8;
-#pragma unroll
-            for (int kk = 0; kk < FD / 16; ++kk) xf[kk] = *reinterpret_cast<const bf16x8_t*>(xr + kk * 16);
-            if constexpr (LN) ln_rows_inplace<FD>(xf, p.ln_g, p.ln_b, p.ln_eps, fh);
-        }
+        xs_load_rows(xf, p.X + rows.clamped(fr) * p.ldx + fh * 8);
+        if constexpr (LN) ln_rows_inplace<FD>(xf, p.ln_g, p.ln_b, p.ln_eps, fh);
         f32x16_t acc[FD / 32];
 #pragma unroll
         for (int nb = 0; nb < FD / 32; ++nb)
@@ -243,23 +398,23 @@ void ff_geglu_fused320_kernel(const FfParams p) {
         // read to just in front of its MFMA to save registers (window of one, `s_waitcnt lgkmcnt(0)` per MFMA pair),
         // and both MFMA phases ran at 64 cycles per MFMA instead of 32.
         constexpr int PD = 4, PD2 = 6;
+        // value / gate fragments of k step kk (rows fr / 32 + fr of the chunk's 64 W1 rows) into slot `slot` of the window
+        auto rd1 = [&](const char* s1, bf16x8_t (&wv)[PD], bf16x8_t (&wg)[PD], int kk, int slot) __attribute__((always_inline)) {
+            wv[slot] = xs_read_frag<64>(s1, kk, fr, fh);
+            wg[slot] = xs_read_frag<64>(s1, kk, 32 + fr, fh);
+        };
         // phase 1 of chunk c: value / gate pre-activations of its 32 channels for this wave's 32 rows
         auto phase1 = [&](int c, f32x16_t& av, f32x16_t& ag) __attribute__((always_inline)) {
             const char* s1 = w1s + (c & 1) * W1_STAGE;
 #pragma unroll
             for (int r = 0; r < 16; ++r) { av[r] = 0.f; ag[r] = 0.f; }
             bf16x8_t wv[PD], wg[PD];
-            auto rd1 = [&](int kk, int slot) __attribute__((always_inline)) {
-                const char* kt = s1 + (kk >> 2) * 8192;
-                wv[slot] = *(lds_vfrag_t*)((lds_char_t*)kt + lds_off128(fr, (kk & 3) * 2 + fh));
-                wg[slot] = *(lds_vfrag_t*)((lds_char_t*)kt + lds_off128(32 + fr, (kk & 3) * 2 + fh));
-            };
 #pragma unroll
-            for (int kk = 0; kk < PD; ++kk) rd1(kk, kk);
+            for (int kk = 0; kk < PD; ++kk) rd1(s1, wv, wg, kk, kk);
 #pragma unroll
             for (int kk = 0; kk < FD / 16; ++kk) {
                 bf16x8_t cv = wv[kk % PD], cg = wg[kk % PD];
-                if (kk + PD < FD / 16) rd1(kk + PD, kk % PD);
+                if (kk + PD < FD / 16) rd1(s1, wv, wg, kk + PD, kk % PD);
                 asm volatile("" : "+v"(cv), "+v"(cg));
                 av = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cv, xf[kk], av, 0, 0, 0);
                 ag = __builtin_amdgcn_mfma_f32_32x32x16_bf16(cg, xf[kk], ag, 0, 0, 0);
@@ -327,13 +482,8 @@ void ff_geglu_fused320_kernel(const FfParams p) {
 #pragma unroll
             for (int r = 0; r < 16; ++r) { nv[r] = 0.f; ng[r] = 0.f; }
             bf16x8_t wv[PD], wg[PD];
-            auto rd1 = [&](int kk, int slot) __attribute__((always_inline)) {
-                const char* kt = s1 + (kk >> 2) * 8192;
-                wv[slot] = *(lds_vfrag_t*)((lds_char_t*)kt + lds_off128(fr, (kk & 3) * 2 + fh));
-                wg[slot] = *(lds_vfrag_t*)((lds_char_t*)kt + lds_off128(32 + fr, (kk & 3) * 2 + fh));
-            };
 #pragma unroll
-            for (int kk = 0; kk < PD; ++kk) rd1(kk, kk);
+            for (int kk = 0; kk < PD; ++kk) rd1(s1, wv, wg, kk, kk);
             // ff1 bias of the 4 channels (quad q = kk / 4) in flight: the gate bias is last used at k step 4 q + 2, the value
             // bias at 4 q + 3; each is reloaded right there for quad q + 1, two k steps ahead of its first use (LDS latency)
             float4 bv = *reinterpret_cast<const float4*>(b1s + c * FCH + 4 * fh);
@@ -346,7 +496,7 @@ void ff_geglu_fused320_kernel(const FfParams p) {
 #pragma unroll
             for (int kk = 0; kk < FD / 16; ++kk) {
                 bf16x8_t fv = wv[kk % PD], fg = wg[kk % PD];
-                if (kk + PD < FD / 16) rd1(kk + PD, kk % PD);
+                if (kk + PD < FD / 16) rd1(s1, wv, wg, kk + PD, kk % PD);
                 asm volatile("" : "+v"(fv), "+v"(fg));
                 const int m = kk >> 1;                    // channel pair (values 2m, 2m + 1 of the accumulators)
                 nv = __builtin_amdgcn_mfma_f32_32x32x16_bf16(fv, xf[kk], nv, 0, 0, 0);
@@ -489,38 +639,26 @@ void ff_geglu_fused320_kernel(const FfParams p) {
         phase2(st, pf, no_t(), no_t(), 0, 0);
         if constexpr (!PROJ) {
             // ---- epilogue: + b2, bf16, + residual; row-major through the wave-private patch (32 rows x 64 B per block)
-            {
-                int lane_e = lane;
-                asm volatile("" : "+v"(lane_e));
-                const int fr_e = lane_e & 31, fh_e = lane_e >> 5;
-                const int rrow = lane_e >> 2, rc = lane_e & 3;
+            int lane_e = lane;
+            asm volatile("" : "+v"(lane_e));
+            const int fr_e = lane_e & 31, fh_e = lane_e >> 5;
+            const int rrow = lane_e >> 2, rc = lane_e & 3;
 #pragma unroll
-                for (int nb = 0; nb < FD / 32; ++nb) {
+            for (int nb = 0; nb < FD / 32; ++nb) {
 #pragma unroll
-                    for (int q = 0; q < 4; ++q) {
-                        const int n = nb * 32 + 8 * q + 4 * fh_e;
-                        const float4 bv = *reinterpret_cast<const float4*>(p.b2 + n);
-                        uint2 pk;
-                        pk.x = pack_bf2(acc[nb][4 * q] + bv.x, acc[nb][4 * q + 1] + bv.y);
-                        pk.y = pack_bf2(acc[nb][4 * q + 2] + bv.z, acc[nb][4 * q + 3] + bv.w);
-                        *reinterpret_cast<uint2*>(ebuf + fr_e * 64 + (((2 * q + fh_e) ^ (((fr_e >> 1) & 3) << 1)) << 3)) = pk;
-                    }
+                for (int q = 0; q < 4; ++q) {
+                    const float4 bv = *reinterpret_cast<const float4*>(p.b2 + nb * 32 + 8 * q + 4 * fh_e);
+                    *xs_patch_acc(ebuf, fr_e, fh_e, q) = xs_pack_acc(acc[nb], q, bv);
+                }
 #pragma unroll
-                    for (int t = 0; t < 2; ++t) {
-                        const int r = t * 16 + rrow;
-                        u32x4_t d = *reinterpret_cast<const u32x4_t*>(ebuf + r * 64 + ((rc ^ ((r >> 1) & 3)) << 4));
-                        const int m = m0 + r;
-                        if (m >= p.M) continue;
-                        const int n = nb * 32 + rc * 8;
-                        if (p.R) {
-                            const u32x4_t rr = *reinterpret_cast<const u32x4_t*>(p.R + (size_t)m * p.ldr + n);
-#pragma unroll
-                            for (int e = 0; e < 4; ++e)
-                                d[e] = pack_bf2(__uint_as_float(d[e] << 16) + __uint_as_float(rr[e] << 16),
-                                                __uint_as_float(d[e] & 0xffff0000u) + __uint_as_float(rr[e] & 0xffff0000u));
-                        }
-                        *reinterpret_cast<u32x4_t*>(p.O + (size_t)m * p.ldo + n) = d;
-                    }
+                for (int t = 0; t < 2; ++t) {
+                    const int r = t * 16 + rrow;
+                    u32x4_t d = *xs_patch_row(ebuf, r, rc);
+                    if (!rows.ok(r)) continue;
+                    const size_t m = rows(r);
+                    const int n = nb * 32 + rc * 8;
+                    if (p.R) xs_add_bf16x8(d, *reinterpret_cast<const u32x4_t*>(p.R + m * p.ldr + n));
+                    *reinterpret_cast<u32x4_t*>(p.O + m * p.ldo + n) = d;
                 }
             }
         } else {
@@ -530,17 +668,12 @@ void ff_geglu_fused320_kernel(const FfParams p) {
             int lane_e = lane;
             asm volatile("" : "+v"(lane_e));
             const int fr_e = lane_e & 31, fh_e = lane_e >> 5;
-            unsigned vo3[5];                             // pieces of a 32-row x 640-byte chunk of Wp (norm_linear's layout);
-#pragma unroll                                           // derived here from the opaque lane id: five more registers held
-            for (int i = 0; i < 5; ++i) {                // across the chunk loop spill
-                const int u = wave * 5 + i;
-                const int t = u >> 2, g = u & 3;
-                vo3[i] = (unsigned)((g * 8 + (lane_e >> 3)) * (FD * 2) + t * 128 + (((lane_e & 7) ^ ((g * 4 + (lane_e >> 4)) & 7)) << 4));
-            }
+            // pieces of a 32-row x 640-byte chunk of Wp (norm_linear's layout), derived here from the opaque lane id and not
+            // pinned: five more registers held across the chunk loop spill
+            unsigned vo3[5];
+            xs_piece_offsets<FD * 2, 128, false>(vo3, wave, lane_e);
             {
-                int mr = m0 + fr_e;
-                if (mr >= p.M) mr = p.M - 1;
-                const bf16_t* rrow = p.R + (size_t)mr * p.ldr + 4 * fh_e;
+                const bf16_t* rrow = p.R + rows.clamped(fr_e) * p.ldr + 4 * fh_e;
 #pragma unroll
                 for (int nb = 0; nb < FD / 32; ++nb) {
                     u32x4_t fw[2];
@@ -567,64 +700,39 @@ void ff_geglu_fused320_kernel(const FfParams p) {
             __builtin_amdgcn_s_barrier();                // every wave is done reading the W rings of the FeedForward
             asm volatile("" ::: "memory");
             auto wp_base = [&](int c) { return (uint64_t)(uintptr_t)p.Wp + (uint64_t)c * (32 * FD * 2); };
-            auto wp_dst = [&](int c, int i) { return lds_base + 2 * W1_STAGE + (c & 1) * W2_STAGE + (wave * 5 + i) * 1024; };
-#pragma unroll
-            for (int i = 0; i < 5; ++i) lds_dma16_sbase(wp_dst(0, i), vo3[i], wp_base(0));
+            auto wp_off = [&](int c) { return 2 * W1_STAGE + (c & 1) * W2_STAGE; };
+            xs_issue_stage(lds_base, wp_off(0), wave, vo3, wp_base(0));
             const bool full_tile = tile * FBM + FBM <= p.M;
+            constexpr int PD3 = 6;                       // LDS read window of the tail's stage loop
             for (int c = 0; c < FD / 32; ++c) {
                 if (c == 0 || !full_tile) wait_vmcnt<0>();
                 else wait_vmcnt<4>();
                 __builtin_amdgcn_s_barrier();
                 asm volatile("" ::: "memory");
-                const char* s3 = w2s + (c & 1) * W2_STAGE;
                 f32x16_t ya;
 #pragma unroll
                 for (int r = 0; r < 16; ++r) ya[r] = 0.f;
-                constexpr int PD3 = 6;
-                bf16x8_t wr[PD3];
-                auto rd3 = [&](int kk, int sl) __attribute__((always_inline)) {
-                    wr[sl] = *(lds_vfrag_t*)((lds_char_t*)s3 + (kk >> 2) * 4096 + lds_off128(fr_e, (kk & 3) * 2 + fh_e));
-                };
-#pragma unroll
-                for (int kk = 0; kk < PD3; ++kk) rd3(kk, kk);
                 const bool more = c + 1 < FD / 32;
                 const uint64_t nbase = wp_base(c + 1);
-#pragma unroll
-                for (int kk = 0; kk < FD / 16; ++kk) {
-                    bf16x8_t f = wr[kk % PD3];
-                    if (kk + PD3 < FD / 16) rd3(kk + PD3, kk % PD3);
-                    asm volatile("" : "+v"(f));
-                    ya = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f, xf[kk], ya, 0, 0, 0);
-                    if (kk < 5 && more) lds_dma16_sbase(wp_dst(c + 1, kk), vo3[kk], nbase);
-                }
+                xs_stage_mma<PD3>(w2s + (c & 1) * W2_STAGE, xf, 0, ya, fr_e, fh_e, [&](int i) __attribute__((always_inline)) {
+                    if (more) lds_dma16_sbase(xs_stage_dst(lds_base, wp_off(c + 1), wave, i), vo3[i], nbase);
+                });
                 // chunk epilogue: + bp, bf16, + R2, row-major through the wave-private patch (32 rows x 64 B)
                 const int n0 = c * 32;
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {
                     const float4 bv = *reinterpret_cast<const float4*>(p.bp + n0 + 8 * q + 4 * fh_e);
-                    uint2 pk;
-                    pk.x = pack_bf2(ya[4 * q] + bv.x, ya[4 * q + 1] + bv.y);
-                    pk.y = pack_bf2(ya[4 * q + 2] + bv.z, ya[4 * q + 3] + bv.w);
-                    *reinterpret_cast<uint2*>(ebuf + fr_e * 64 + (((2 * q + fh_e) ^ (((fr_e >> 1) & 3) << 1)) << 3)) = pk;
+                    *xs_patch_acc(ebuf, fr_e, fh_e, q) = xs_pack_acc(ya, q, bv);
                 }
                 const int rrow2 = lane_e >> 2, rc = lane_e & 3;
                 u32x4_t rres[2];
-                int mrow[2];
-#pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    mrow[t] = m0 + t * 16 + rrow2;
-                    const int mc = mrow[t] < p.M ? mrow[t] : p.M - 1;
-                    rres[t] = *reinterpret_cast<const u32x4_t*>(p.R2 + (size_t)mc * p.ldr2 + n0 + rc * 8);
-                }
+                xs_load_chunk_rows(rres, p.R2, p.ldr2, rows, n0, lane_e);
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
                     const int r = t * 16 + rrow2;
-                    u32x4_t d = *reinterpret_cast<const u32x4_t*>(ebuf + r * 64 + ((rc ^ ((r >> 1) & 3)) << 4));
-#pragma unroll
-                    for (int e = 0; e < 4; ++e)
-                        d[e] = pack_bf2(__uint_as_float(d[e] << 16) + __uint_as_float(rres[t][e] << 16),
-                                        __uint_as_float(d[e] & 0xffff0000u) + __uint_as_float(rres[t][e] & 0xffff0000u));
-                    if (mrow[t] < p.M) *reinterpret_cast<u32x4_t*>(p.O2 + (size_t)mrow[t] * p.ldo2 + n0 + rc * 8) = d;
+                    u32x4_t d = *xs_patch_row(ebuf, r, rc);
+                    xs_add_bf16x8(d, rres[t]);
+                    if (rows.ok(r)) *reinterpret_cast<u32x4_t*>(p.O2 + rows(r) * p.ldo2 + n0 + rc * 8) = d;
                 }
             }
             wait_vmcnt<0>();
@@ -652,8 +760,6 @@ void ff_geglu_fused320_kernel(const FfParams p) {
 // at the head of a tile and the stores of the epilogue. At K = 320 the kernel is bound by the HBM writes of `out`, not by
 // the matrix pipe. A launch with few row tiles splits N over `nsplit` workgroups per tile (level 1: 576 tiles for 512
 // slots would leave the second round almost empty).
-constexpr int LCH = 32;                        // output channels per chunk
-constexpr int LW_STAGE = LCH * FD * 2;         // 20 KB: 5 K tiles of [32 rows][128 B]
 constexpr int LL_BIAS = 640;                   // bias entries kept in LDS (N <= 640: every bias-carrying use in the UNet)
 // ring + epilogue patches + gamma / beta + bias (K = 320: 54272 B, three workgroups per CU still fit the 160 KB)
 constexpr int ll_lds(int kh) { return 2 * LW_STAGE + 4 * 2048 + 2 * FD * kh * 4 + LL_BIAS * 4; }
@@ -682,56 +788,30 @@ void norm_linear_kernel(const LlParams p) {
     const int fr = lane & 31, fh = lane >> 5;
     const unsigned lds_base = (unsigned)(unsigned long)((lds_char_t*)smem);
     char* const ebuf = smem + 2 * LW_STAGE + wave * 2048;
-    // the nsplit workgroups of a row tile read the same activation rows: they are 8 block ids apart, i.e. on one XCD at about the
-    // same time, so that the second read is an L2 hit (consecutive ids go to different XCDs: counters showed X fetched nsplit times)
-    const int bgrp = (int)blockIdx.x / (8 * p.nsplit), brem = (int)blockIdx.x - bgrp * (8 * p.nsplit);
-    const int tile = bgrp * 8 + (brem & 7), part = brem >> 3;
+    const XsPart part = xs_part_decode(p.nsplit, p.cpp, p.N / LCH);
+    const int tile = part.tile, c_begin = part.c_begin, c_end = part.c_end;
     if (tile * FBM >= p.M) return;                                   // padding blocks of the last group of 8 tiles
-    const int m0 = tile * FBM + wave * 32;
+    const XsRowsLinear rows{tile * FBM + wave * 32, p.M};
     const bool full_tile = tile * FBM + FBM <= p.M;                    // ragged last tile: uncounted vmcnt waits
-    const int c_begin = part * p.cpp;
-    int c_end = c_begin + p.cpp;
-    if (c_end > p.N / LCH) c_end = p.N / LCH;
     if (c_begin >= c_end) return;
 
     // LDS-DMA of stage (chunk c, k half h): 32 weight rows x 640 B = 20 pieces of 8 rows x 128 B, 5 per wave
     unsigned vo[5];
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-        const int u = wave * 5 + i;                      // (K tile t, 8-row group g): LDS offset u * 1024
-        const int t = u >> 2, g = u & 3;
-        vo[i] = (unsigned)((g * 8 + (lane >> 3)) * (KD * 2) + t * 128 + (((lane & 7) ^ ((g * 4 + (lane >> 4)) & 7)) << 4));
-        asm volatile("" : "+v"(vo[i]));
-    }
+    xs_piece_offsets<KD * 2, 128>(vo, wave, lane);
     auto w_base = [&](int c, int h) { return (uint64_t)(uintptr_t)p.W + (uint64_t)c * (LCH * KD * 2) + h * (FD * 2); };
-    auto w_dst = [&](int slot, int i) { return lds_base + slot * LW_STAGE + (wave * 5 + i) * 1024; };
-
-#pragma unroll
-    for (int i = 0; i < 5; ++i) lds_dma16_sbase(w_dst(0, i), vo[i], w_base(c_begin, 0));
+    xs_issue_stage(lds_base, 0, wave, vo, w_base(c_begin, 0));
 
     // ---- X fragments of this wave's 32 rows (B operand: lane (row fr, half fh) holds k = 16 kk + 8 fh .. + 7)
     bf16x8_t xf[KD / 16];
     float* const lns = reinterpret_cast<float*>(smem + 2 * LW_STAGE + 4 * 2048);
     float* const bls = lns + 2 * KD;
     const bool bias_lds = p.bias != nullptr && p.N <= LL_BIAS;
-    {
-        int mr = m0 + fr;
-        if (mr >= p.M) mr = p.M - 1;
-        const bf16_t* xr = p.X + (size_t)mr * p.ldx + fh * 8;
-#pragma unroll
-        for (int kk = 0; kk < KD / 16; ++kk) xf[kk] = *reinterpret_cast<const bf16x8_t*>(xr + kk * 16);
-        // the bias in LDS: as global loads in the chunk epilogue they were two exposed round trips per 20 MFMAs
-        if (bias_lds) for (int i = tid; i < p.N; i += 256) bls[i] = p.bias[i];
-        if constexpr (NORM == 1) {
-            for (int i = tid; i < KD; i += 256) { lns[i] = p.ln_g[i]; lns[KD + i] = p.ln_b[i]; }
-        } else if constexpr (NORM == 2) {
-            const int inst = (int)(((long long)tile * FBM) / p.gn_rpi);           // a tile never straddles two instances
-            for (int i = tid; i < KD; i += 256) {
-                const float2 st = p.gn_stats[(size_t)inst * p.gn_groups + i / (KD / p.gn_groups)];
-                const float a = p.ln_g[i] * st.y;
-                lns[i] = a; lns[KD + i] = p.ln_b[i] - st.x * a;
-            }
-        }
+    xs_load_rows(xf, p.X + rows.clamped(fr) * p.ldx + fh * 8);
+    if (bias_lds) xs_stage_bias(bls, p.bias, p.N, tid);
+    if constexpr (NORM == 1) xs_stage_ln_affine(lns, KD, p.ln_g, p.ln_b, tid);
+    if constexpr (NORM == 2) {
+        const int inst = (int)(((long long)tile * FBM) / p.gn_rpi);           // a tile never straddles two instances
+        xs_stage_gn_affine(lns, KD, p.ln_g, p.ln_b, p.gn_stats + (size_t)inst * p.gn_groups, p.gn_groups, tid);
     }
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");     // X, gamma / beta and the first stage: the compiler's own
     __builtin_amdgcn_s_barrier();                                   // vmcnt accounting does not see the asm LDS-DMA, so the
@@ -759,70 +839,37 @@ void norm_linear_kernel(const LlParams p) {
             if constexpr (RES) {
                 // the residual rows of this chunk, in the coalesced pattern of the stores (16 rows x 64 B per instruction),
                 // requested a chunk's MFMAs ahead of the epilogue that adds them
-                if (h == 0) {
-#pragma unroll
-                    for (int t = 0; t < 2; ++t) {
-                        int m = m0 + t * 16 + (lane >> 2);
-                        if (m >= p.M) m = p.M - 1;
-                        rres[t] = *reinterpret_cast<const u32x4_t*>(p.R + (size_t)m * p.ldr + c * LCH + (lane & 3) * 8);
-                    }
-                }
+                if (h == 0) xs_load_chunk_rows(rres, p.R, p.ldr, rows, c * LCH, lane);
             }
-            const char* s1 = smem + slot * LW_STAGE;
-            bf16x8_t wr[PD];
-            auto rd = [&](int kk, int sl) __attribute__((always_inline)) {
-                wr[sl] = *(lds_vfrag_t*)((lds_char_t*)s1 + (kk >> 2) * 4096 + lds_off128(fr, (kk & 3) * 2 + fh));
-            };
-#pragma unroll
-            for (int kk = 0; kk < PD; ++kk) rd(kk, kk);
             const bool more = h + 1 < KH || c + 1 < c_end;
             const uint64_t nb = h + 1 < KH ? w_base(c, h + 1) : w_base(c + 1, 0);
-#pragma unroll
-            for (int kk = 0; kk < FD / 16; ++kk) {
-                bf16x8_t f = wr[kk % PD];
-                if (kk + PD < FD / 16) rd(kk + PD, kk % PD);
-                asm volatile("" : "+v"(f));
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f, xf[h * (FD / 16) + kk], acc, 0, 0, 0);
-                if (kk < 5 && more) lds_dma16_sbase(w_dst(slot ^ 1, kk), vo[kk], nb);
-            }
+            xs_stage_mma<PD>(smem + slot * LW_STAGE, xf, h * (FD / 16), acc, fr, fh, [&](int i) __attribute__((always_inline)) {
+                if (more) lds_dma16_sbase(xs_stage_dst(lds_base, (slot ^ 1) * LW_STAGE, wave, i), vo[i], nb);
+            });
             slot ^= 1;
         }
-        // ---- chunk epilogue: + bias, bf16, row-major 16-byte stores through the wave-private patch (32 rows x 64 B)
+        // ---- chunk epilogue: + bias (+ residual), bf16, row-major 16-byte stores through the wave-private patch
         {
             const int n0 = c * LCH;
             const int rrow = lane >> 2, rc = lane & 3;
             if constexpr (RES) {
-                // residual through the patch the other way round: row-major in, accumulator layout out - the sum is formed in
-                // fp32 and rounded to bf16 once, as the tile GEMM's residual epilogue does (one wave's LDS operations execute in
-                // order: no barrier)
 #pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    const int r = t * 16 + rrow;
-                    *reinterpret_cast<u32x4_t*>(ebuf + r * 64 + ((rc ^ ((r >> 1) & 3)) << 4)) = rres[t];
-                }
+                for (int t = 0; t < 2; ++t) *xs_patch_row(ebuf, t * 16 + rrow, rc) = rres[t];
             }
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 float4 bv = {0.f, 0.f, 0.f, 0.f};
                 if (bias_lds) bv = *reinterpret_cast<const float4*>(bls + n0 + 8 * q + 4 * fh);
                 else if (p.bias) bv = *reinterpret_cast<const float4*>(p.bias + n0 + 8 * q + 4 * fh);
-                uint2* const slot = reinterpret_cast<uint2*>(ebuf + fr * 64 + (((2 * q + fh) ^ (((fr >> 1) & 3) << 1)) << 3));
-                if constexpr (RES) {
-                    const uint2 rv = *slot;
-                    bv.x += __uint_as_float(rv.x << 16); bv.y += __uint_as_float(rv.x & 0xffff0000u);
-                    bv.z += __uint_as_float(rv.y << 16); bv.w += __uint_as_float(rv.y & 0xffff0000u);
-                }
-                uint2 pk;
-                pk.x = pack_bf2(acc[4 * q] + bv.x, acc[4 * q + 1] + bv.y);
-                pk.y = pack_bf2(acc[4 * q + 2] + bv.z, acc[4 * q + 3] + bv.w);
-                *slot = pk;
+                uint2* const slot = xs_patch_acc(ebuf, fr, fh, q);
+                if constexpr (RES) xs_add_bf16x4(bv, *slot);
+                *slot = xs_pack_acc(acc, q, bv);
             }
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 const int r = t * 16 + rrow;
-                const u32x4_t d = *reinterpret_cast<const u32x4_t*>(ebuf + r * 64 + ((rc ^ ((r >> 1) & 3)) << 4));
-                const int m = m0 + r;
-                if (m < p.M) *reinterpret_cast<u32x4_t*>(p.O + (size_t)m * p.ldo + n0 + rc * 8) = d;
+                const u32x4_t d = *xs_patch_row(ebuf, r, rc);
+                if (rows.ok(r)) *reinterpret_cast<u32x4_t*>(p.O + rows(r) * p.ldo + n0 + rc * 8) = d;
             }
         }
     }
@@ -878,39 +925,26 @@ void ln_qkv_tattn_kernel(const TaParams p) {
     float* const lns = reinterpret_cast<float*>(smem + NS * LW_STAGE + 4 * TA_PATCH);
     const int gpb = p.HW >> 3;                                    // 8-position groups per clip
     const int b = (int)blockIdx.x / gpb, p0 = ((int)blockIdx.x - b * gpb) * 8 + 2 * wave;
-    auto grow = [&](int r) { return ((size_t)(b * 16 + (r & 15))) * p.HW + p0 + (r >> 4); };      // wave row r -> tensor row
+    const XsRowsGather grow{b, p.HW, p0};                        // wave row r -> tensor row
 
     unsigned vo[5];
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-        const int u = wave * 5 + i;
-        const int t = u >> 2, g = u & 3;
-        vo[i] = (unsigned)((g * 8 + (lane >> 3)) * (KD * 2) + t * 128 + (((lane & 7) ^ ((g * 4 + (lane >> 4)) & 7)) << 4));
-        asm volatile("" : "+v"(vo[i]));
-    }
+    xs_piece_offsets<KD * 2, 128>(vo, wave, lane);
     // chunk (head h, part): part 0,1 = q halves, 2,3 = k halves, 4,5 = v halves -> weight rows (part/2) * C + 64 h + 32 (part&1);
     // stage (chunk, kh): the k half kh of those rows
     auto w_base = [&](int h, int part, int kh) {
         return (uint64_t)(uintptr_t)p.W + (uint64_t)((part >> 1) * KD + 64 * h + 32 * (part & 1)) * (KD * 2) + (uint64_t)kh * (FD * 2);
     };
-    auto w_dst = [&](int slot, int i) { return lds_base + slot * LW_STAGE + (wave * 5 + i) * 1024; };
 
     // gridDim.y workgroups share the heads of a row tile (DC_TA_HSPLIT=2 at dim 640: heads 0-4 / 5-9, x read twice - no faster)
     const int hpw = 5 * KH / (int)gridDim.y;
     const int h_begin = (int)blockIdx.y * hpw, h_end = h_begin + hpw;
     // stage index inside a head: lin = part * KH + kh (compile-time in the unrolled loops below)
 #pragma unroll
-    for (int d = 0; d < NS - 1; ++d)
-#pragma unroll
-        for (int i = 0; i < 5; ++i) lds_dma16_sbase(w_dst(d, i), vo[i], w_base(h_begin + d / SPH, (d % SPH) / KH, d % KH));
+    for (int d = 0; d < NS - 1; ++d) xs_issue_stage(lds_base, d * LW_STAGE, wave, vo, w_base(h_begin + d / SPH, (d % SPH) / KH, d % KH));
 
     bf16x8_t xf[KD / 16];
-    {
-        const bf16_t* xr = p.X + grow(fr) * p.ldx + fh * 8;
-#pragma unroll
-        for (int kk = 0; kk < KD / 16; ++kk) xf[kk] = *reinterpret_cast<const bf16x8_t*>(xr + kk * 16);
-        for (int i = tid; i < KD; i += 256) { lns[i] = p.ln_g[i]; lns[KD + i] = p.ln_b[i]; }
-    }
+    xs_load_rows(xf, p.X + grow(fr) * p.ldx + fh * 8);
+    xs_stage_ln_affine(lns, KD, p.ln_g, p.ln_b, tid);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
@@ -945,26 +979,14 @@ void ln_qkv_tattn_kernel(const TaParams p) {
                     __builtin_amdgcn_s_barrier();
                     asm volatile("" ::: "memory");
                 }
-                const char* s1 = smem + slot * LW_STAGE;
-                bf16x8_t wr[PD];
-                auto rd = [&](int kk, int sl) __attribute__((always_inline)) {
-                    wr[sl] = *(lds_vfrag_t*)((lds_char_t*)s1 + (kk >> 2) * 4096 + lds_off128(fr, (kk & 3) * 2 + fh));
-                };
-#pragma unroll
-                for (int kk = 0; kk < PD; ++kk) rd(kk, kk);
                 // the stage NS - 1 ahead goes into the slot that stage lin - 1 has just left (every wave is past this stage's barrier)
                 const int nl = lin + NS - 1;
                 const int nh = h + nl / SPH;
                 const bool more = nh < h_end;
                 const uint64_t nb = w_base(nh, (nl % SPH) / KH, nl % KH);
-#pragma unroll
-                for (int kk = 0; kk < FD / 16; ++kk) {
-                    bf16x8_t f = wr[kk % PD];
-                    if (kk + PD < FD / 16) rd(kk + PD, kk % PD);
-                    asm volatile("" : "+v"(f));
-                    acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f, xf[kh * (FD / 16) + kk], acc, 0, 0, 0);
-                    if (kk < 5 && more) lds_dma16_sbase(w_dst(nl % NS, kk), vo[kk], nb);
-                }
+                xs_stage_mma<PD>(smem + slot * LW_STAGE, xf, kh * (FD / 16), acc, fr, fh, [&](int i) __attribute__((always_inline)) {
+                    if (more) lds_dma16_sbase(xs_stage_dst(lds_base, (nl % NS) * LW_STAGE, wave, i), vo[i], nb);
+                });
             }
             if (part < 4) {
                 // q / k block of this row: the two operand fragments of k steps 2 (part & 1), + 1
@@ -1059,12 +1081,12 @@ void ln_qkv_tattn_kernel(const TaParams p) {
 
 
 // ---------------------------------------------------------------------------------------------------------------------
-// GroupNorm (known statistics) + SiLU + temporal convolution (3,1,1) (+ residual) for 320 channels in ONE launch:
+// GroupNorm (known statistics) + SiLU + temporal convolution (3,1,1) (+ residual) for 320 / 640 channels in ONE launch:
 //   out[b, f, p, :] = bias + sum_t W_t a[b, f + t - 1, p, :] (zero outside the clip),  a = silu(GroupNorm(x))
 //   reference: TemporalConvBlock lvdm/modules/networks/openaimodel3d.py:239-279 (conv1..conv4 = GroupNorm(32) -> SiLU ->
 //   Conv3d (3,1,1), zero padding in time); the block's `identity + x` (:279) rides on the last conv as `residual`.
 // As GroupNorm (statistics, apply) + implicit GEMM the activated copy is written, then read three times (once per tap)
-// through the L2. Here the rows are gathered as in ln_qkv_tattn320_kernel: a wave owns 2 positions x 16 frames, so the
+// through the L2. Here the rows are gathered as in ln_qkv_tattn_kernel: a wave owns 2 positions x 16 frames, so the
 // frames f - 1 and f + 1 of a row are its NEIGHBOUR LANES. The normalised, activated X fragments stay in registers; per
 // 32-column chunk three products Y_t = X W_t^T (the same X, 20 MFMAs each) and
 //   out[f] = Y_0[f - 1] + Y_1[f] + Y_2[f + 1]
@@ -1096,50 +1118,30 @@ void gn_silu_tconv_kernel(const TcParams p) {
     float* const lns = reinterpret_cast<float*>(smem + 2 * LW_STAGE + 4 * 2048);
     float* const bls = lns + 2 * KD;                     // the bias in LDS (as in norm_linear_kernel)
     const bool bias_lds = KH == 1 && p.N <= LL_BIAS;     // (C = 640 sits at 256 registers: it keeps its loads in the epilogue)
-    const int bgrp = (int)blockIdx.x / (8 * p.nsplit), brem = (int)blockIdx.x - bgrp * (8 * p.nsplit);
-    const int tile = bgrp * 8 + (brem & 7), part = brem >> 3;      // the parts of a tile on one XCD (see norm_linear_kernel)
+    const XsPart part = xs_part_decode(p.nsplit, p.cpp, p.N / LCH);      // the parts of a tile on one XCD
+    const int tile = part.tile, c_begin = part.c_begin, c_end = part.c_end;
     if (tile >= p.ntiles) return;
     const int gpb = p.HW >> 3;
     const int b = tile / gpb, p0 = (tile - b * gpb) * 8 + 2 * wave;
-    auto grow = [&](int r) { return ((size_t)(b * 16 + (r & 15))) * p.HW + p0 + (r >> 4); };      // wave row r -> tensor row
-    const int c_begin = part * p.cpp;
-    int c_end = c_begin + p.cpp;
-    if (c_end > p.N / LCH) c_end = p.N / LCH;
+    const XsRowsGather grow{b, p.HW, p0};                // wave row r -> tensor row
     if (c_begin >= c_end) return;
 
     // LDS-DMA of stage (chunk c, tap t, k half h): 32 weight rows x 320 channels of the tap = 5 K tiles of [32 rows][128 B];
     // in the packed weight the K tile of 64-channel slice s and tap t starts at column 192 s + 64 t
     unsigned vo[5];
-#pragma unroll
-    for (int i = 0; i < 5; ++i) {
-        const int u = wave * 5 + i;
-        const int t = u >> 2, g = u & 3;
-        vo[i] = (unsigned)((g * 8 + (lane >> 3)) * (3 * KD * 2) + t * 384 + (((lane & 7) ^ ((g * 4 + (lane >> 4)) & 7)) << 4));
-        asm volatile("" : "+v"(vo[i]));
-    }
+    xs_piece_offsets<3 * KD * 2, 384>(vo, wave, lane);
     // stage index within a chunk: j = 0 .. 3 KH - 1, tap = order[j / KH], half = j % KH
     auto w_base = [&](int c, int j) {
         const int jt = j / KH, h = j - jt * KH;
         const int tap = jt == 0 ? 1 : (jt == 1 ? 0 : 2);
         return (uint64_t)(uintptr_t)p.W + (uint64_t)c * (LCH * 3 * KD * 2) + tap * 128 + h * (5 * 384);
     };
-    auto w_dst = [&](int slot, int i) { return lds_base + slot * LW_STAGE + (wave * 5 + i) * 1024; };
-
-#pragma unroll
-    for (int i = 0; i < 5; ++i) lds_dma16_sbase(w_dst(0, i), vo[i], w_base(c_begin, 0));
+    xs_issue_stage(lds_base, 0, wave, vo, w_base(c_begin, 0));
 
     bf16x8_t xf[KD / 16];
-    {
-        const bf16_t* xr = p.X + grow(fr) * p.ldx + fh * 8;
-#pragma unroll
-        for (int kk = 0; kk < KD / 16; ++kk) xf[kk] = *reinterpret_cast<const bf16x8_t*>(xr + kk * 16);
-        for (int i = tid; i < KD; i += 256) {            // one clip per workgroup: a = gamma rstd, b = beta - mean a
-            const float2 st = p.gn_stats[(size_t)b * p.gn_groups + i / (KD / p.gn_groups)];
-            const float a = p.gn_g[i] * st.y;
-            lns[i] = a; lns[KD + i] = p.gn_b[i] - st.x * a;
-        }
-        if (bias_lds) for (int i = tid; i < p.N; i += 256) bls[i] = p.bias[i];
-    }
+    xs_load_rows(xf, p.X + grow(fr) * p.ldx + fh * 8);
+    xs_stage_gn_affine(lns, KD, p.gn_g, p.gn_b, p.gn_stats + (size_t)b * p.gn_groups, p.gn_groups, tid);      // one clip per workgroup
+    if (bias_lds) xs_stage_bias(bls, p.bias, p.N, tid);
     asm volatile("s_waitcnt vmcnt(0) lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_s_barrier();
     asm volatile("" ::: "memory");
@@ -1170,28 +1172,16 @@ void gn_silu_tconv_kernel(const TcParams p) {
                         rres[t] = *reinterpret_cast<const u32x4_t*>(p.R + grow(t * 16 + (lane >> 2)) * p.ldr + c * LCH + (lane & 3) * 8);
                 }
             }
-            const char* s1 = smem + slot * LW_STAGE;
             f32x16_t& acc = jt == 0 ? out : y;
             if (h == 0) {
 #pragma unroll
                 for (int r = 0; r < 16; ++r) acc[r] = 0.f;
             }
-            bf16x8_t wr[PD];
-            auto rd = [&](int kk, int sl) __attribute__((always_inline)) {
-                wr[sl] = *(lds_vfrag_t*)((lds_char_t*)s1 + (kk >> 2) * 4096 + lds_off128(fr, (kk & 3) * 2 + fh));
-            };
-#pragma unroll
-            for (int kk = 0; kk < PD; ++kk) rd(kk, kk);
             const bool more = j + 1 < NS || c + 1 < c_end;
             const uint64_t nb = j + 1 < NS ? w_base(c, j + 1) : w_base(c + 1, 0);
-#pragma unroll
-            for (int kk = 0; kk < FD / 16; ++kk) {
-                bf16x8_t f = wr[kk % PD];
-                if (kk + PD < FD / 16) rd(kk + PD, kk % PD);
-                asm volatile("" : "+v"(f));
-                acc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(f, xf[h * (FD / 16) + kk], acc, 0, 0, 0);
-                if (kk < 5 && more) lds_dma16_sbase(w_dst(slot ^ 1, kk), vo[kk], nb);
-            }
+            xs_stage_mma<PD>(smem + slot * LW_STAGE, xf, h * (FD / 16), acc, fr, fh, [&](int i) __attribute__((always_inline)) {
+                if (more) lds_dma16_sbase(xs_stage_dst(lds_base, (slot ^ 1) * LW_STAGE, wave, i), vo[i], nb);
+            });
             slot ^= 1;
             if (jt > 0 && h == KH - 1) {
                 // out[f] += Y_0[f - 1] (row_shr:1) resp. Y_2[f + 1] (row_shl:1): the 16 lanes of a DPP row are the 16 frames
@@ -1214,33 +1204,21 @@ void gn_silu_tconv_kernel(const TcParams p) {
 #pragma unroll
                     for (int t = 0; t < 2; ++t) rres[t] = *reinterpret_cast<const u32x4_t*>(p.R + grow(t * 16 + rrow) * p.ldr + n0 + rc * 8);
                 }
-                // residual through the patch the other way round (row-major in, accumulator layout out): the sum is formed in
-                // fp32 and rounded once
 #pragma unroll
-                for (int t = 0; t < 2; ++t) {
-                    const int r = t * 16 + rrow;
-                    *reinterpret_cast<u32x4_t*>(ebuf + r * 64 + ((rc ^ ((r >> 1) & 3)) << 4)) = rres[t];
-                }
+                for (int t = 0; t < 2; ++t) *xs_patch_row(ebuf, t * 16 + rrow, rc) = rres[t];
             }
 #pragma unroll
             for (int q = 0; q < 4; ++q) {
                 float4 bv = bias_lds ? *reinterpret_cast<const float4*>(bls + n0 + 8 * q + 4 * fh)
                                      : *reinterpret_cast<const float4*>(p.bias + n0 + 8 * q + 4 * fh);
-                uint2* const slot2 = reinterpret_cast<uint2*>(ebuf + fr * 64 + (((2 * q + fh) ^ (((fr >> 1) & 3) << 1)) << 3));
-                if constexpr (RES) {
-                    const uint2 rv = *slot2;
-                    bv.x += __uint_as_float(rv.x << 16); bv.y += __uint_as_float(rv.x & 0xffff0000u);
-                    bv.z += __uint_as_float(rv.y << 16); bv.w += __uint_as_float(rv.y & 0xffff0000u);
-                }
-                uint2 pk;
-                pk.x = pack_bf2(out[4 * q] + bv.x, out[4 * q + 1] + bv.y);
-                pk.y = pack_bf2(out[4 * q + 2] + bv.z, out[4 * q + 3] + bv.w);
-                *slot2 = pk;
+                uint2* const slot2 = xs_patch_acc(ebuf, fr, fh, q);
+                if constexpr (RES) xs_add_bf16x4(bv, *slot2);
+                *slot2 = xs_pack_acc(out, q, bv);
             }
 #pragma unroll
             for (int t = 0; t < 2; ++t) {
                 const int r = t * 16 + rrow;
-                const u32x4_t d = *reinterpret_cast<const u32x4_t*>(ebuf + r * 64 + ((rc ^ ((r >> 1) & 3)) << 4));
+                const u32x4_t d = *xs_patch_row(ebuf, r, rc);
                 *reinterpret_cast<u32x4_t*>(p.O + grow(r) * p.ldo + n0 + rc * 8) = d;
             }
         }
@@ -1314,15 +1292,20 @@ static int launch_norm_linear_t(const LlParams& p, dim3 grid, hipStream_t stream
     return 0;
 }
 
-static int launch_norm_linear(int norm, int K, LlParams& p, hipStream_t stream) {
-    // few row tiles: split N over several workgroups per tile until the launch has >= 3 rounds of work for its slots
-    const int tiles = (p.M + FBM - 1) / FBM, nch = p.N / LCH;
-    const int slots = 256 * (K == FD ? 3 : 2);
+// The split-N launches (xs_part_decode is the device side). Few row tiles: N is split over several workgroups per tile until
+// the launch has >= 3 rounds of work for its `slots` resident workgroups, with at least 5 chunks per workgroup.
+struct XsSplit { int nsplit, cpp; dim3 grid; };
+static XsSplit xs_split_n(int tiles, int nch, int slots) {
     int nsplit = 1;
     while (tiles * nsplit < 3 * slots && nsplit * 2 <= nch && nch / (nsplit * 2) >= 5) nsplit *= 2;
-    p.nsplit = nsplit;
-    p.cpp = (nch + nsplit - 1) / nsplit;
-    const dim3 grid((tiles + 7) / 8 * 8 * nsplit);
+    return {nsplit, (nch + nsplit - 1) / nsplit, dim3((unsigned)((tiles + 7) / 8 * 8 * nsplit))};
+}
+
+static int launch_norm_linear(int norm, int K, LlParams& p, hipStream_t stream) {
+    const XsSplit sp = xs_split_n((p.M + FBM - 1) / FBM, p.N / LCH, 256 * (K == FD ? 3 : 2));
+    p.nsplit = sp.nsplit;
+    p.cpp = sp.cpp;
+    const dim3 grid = sp.grid;
     if (p.R) return K == FD ? launch_norm_linear_t<0, 1, true>(p, grid, stream) : launch_norm_linear_t<0, 2, true>(p, grid, stream);
     if (K == FD) {
         if (norm == 1) return launch_norm_linear_t<1, 1>(p, grid, stream);
@@ -1334,26 +1317,32 @@ static int launch_norm_linear(int norm, int K, LlParams& p, hipStream_t stream) 
     return launch_norm_linear_t<0, 2>(p, grid, stream);
 }
 
+// The checks and fields the three entries of norm_linear_kernel share; p comes back as a plain Linear (no norm, no residual)
+static int ll_params(LlParams& p, const uint16_t* x, int ldx, int K, const uint16_t* w, const float* bias, uint16_t* out, int ldo,
+                     int M, int N) {
+    if ((K != FD && K != 2 * FD) || M < 1 || N < LCH || N % LCH || ldx % 8 || ldo % 8) return DC_ERR_SHAPE;
+    if (((uintptr_t)x | (uintptr_t)out | (uintptr_t)w) % 16) return DC_ERR_SHAPE;
+    p.X = x; p.ldx = ldx; p.W = w; p.bias = bias; p.O = out; p.ldo = ldo; p.M = M; p.N = N;
+    p.ln_g = nullptr; p.ln_b = nullptr; p.ln_eps = 0.f; p.gn_stats = nullptr; p.gn_groups = 1; p.gn_rpi = FBM;
+    p.R = nullptr; p.ldr = 0;
+    return 0;
+}
+
 extern "C" int dc_ln_linear(const uint16_t* x, int ldx, int K, const float* ln_gamma, const float* ln_beta, float ln_eps,
                             const uint16_t* w, const float* bias, uint16_t* out, int ldo, int M, int N, void* stream_) {
     if (!x || !w || !out || ((ln_gamma == nullptr) != (ln_beta == nullptr))) return DC_ERR_ARG;
-    if ((K != FD && K != 2 * FD) || M < 1 || N < LCH || N % LCH || ldx % 8 || ldo % 8) return DC_ERR_SHAPE;
-    if (((uintptr_t)x | (uintptr_t)out | (uintptr_t)w) % 16) return DC_ERR_SHAPE;
     LlParams p;
-    p.X = x; p.ldx = ldx; p.W = w; p.bias = bias; p.O = out; p.ldo = ldo; p.M = M; p.N = N;
-    p.ln_g = ln_gamma; p.ln_b = ln_beta; p.ln_eps = ln_eps; p.gn_stats = nullptr; p.gn_groups = 1; p.gn_rpi = FBM;
-    p.R = nullptr; p.ldr = 0;
+    if (const int e = ll_params(p, x, ldx, K, w, bias, out, ldo, M, N)) return e;
+    p.ln_g = ln_gamma; p.ln_b = ln_beta; p.ln_eps = ln_eps;
     return launch_norm_linear(ln_gamma ? 1 : 0, K, p, (hipStream_t)stream_);
 }
 
 extern "C" int dc_linear_residual(const uint16_t* x, int ldx, int K, const uint16_t* w, const float* bias,
                                   const uint16_t* residual, int ldr, uint16_t* out, int ldo, int M, int N, void* stream_) {
     if (!x || !w || !out || !residual) return DC_ERR_ARG;
-    if ((K != FD && K != 2 * FD) || M < 1 || N < LCH || N % LCH || ldx % 8 || ldo % 8 || ldr % 8) return DC_ERR_SHAPE;
-    if (((uintptr_t)x | (uintptr_t)out | (uintptr_t)w | (uintptr_t)residual) % 16) return DC_ERR_SHAPE;
     LlParams p;
-    p.X = x; p.ldx = ldx; p.W = w; p.bias = bias; p.O = out; p.ldo = ldo; p.M = M; p.N = N;
-    p.ln_g = nullptr; p.ln_b = nullptr; p.ln_eps = 0.f; p.gn_stats = nullptr; p.gn_groups = 1; p.gn_rpi = FBM;
+    if (const int e = ll_params(p, x, ldx, K, w, bias, out, ldo, M, N)) return e;
+    if (ldr % 8 || (uintptr_t)residual % 16) return DC_ERR_SHAPE;
     p.R = residual; p.ldr = ldr;
     return launch_norm_linear(0, K, p, (hipStream_t)stream_);
 }
@@ -1362,14 +1351,11 @@ extern "C" int dc_gn_linear(const uint16_t* x, int ldx, int K, const float* gamm
                             int groups, int rows_per_inst, const uint16_t* w, const float* bias, uint16_t* out, int ldo,
                             int M, int N, void* stream_) {
     if (!x || !w || !out || !gamma || !beta || !stats) return DC_ERR_ARG;
-    if ((K != FD && K != 2 * FD) || M < 1 || N < LCH || N % LCH || ldx % 8 || ldo % 8) return DC_ERR_SHAPE;
-    if (groups < 1 || K % groups || rows_per_inst < FBM || rows_per_inst % FBM || M % rows_per_inst) return DC_ERR_SHAPE;
-    if (((uintptr_t)x | (uintptr_t)out | (uintptr_t)w) % 16) return DC_ERR_SHAPE;
     LlParams p;
-    p.X = x; p.ldx = ldx; p.W = w; p.bias = bias; p.O = out; p.ldo = ldo; p.M = M; p.N = N;
-    p.ln_g = gamma; p.ln_b = beta; p.ln_eps = 0.f;
+    if (const int e = ll_params(p, x, ldx, K, w, bias, out, ldo, M, N)) return e;
+    if (groups < 1 || K % groups || rows_per_inst < FBM || rows_per_inst % FBM || M % rows_per_inst) return DC_ERR_SHAPE;
+    p.ln_g = gamma; p.ln_b = beta;
     p.gn_stats = reinterpret_cast<const float2*>(stats); p.gn_groups = groups; p.gn_rpi = rows_per_inst;
-    p.R = nullptr; p.ldr = 0;
     return launch_norm_linear(2, K, p, (hipStream_t)stream_);
 }
 
@@ -1423,12 +1409,10 @@ extern "C" int dc_gn_silu_tconv3(const uint16_t* x, int ldx, int C, const float*
     TcParams p;
     p.X = x; p.ldx = ldx; p.W = w; p.bias = bias; p.R = residual; p.ldr = ldr; p.O = out; p.ldo = ldo;
     p.gn_g = gamma; p.gn_b = beta; p.gn_stats = reinterpret_cast<const float2*>(stats); p.gn_groups = groups; p.HW = HW; p.N = N;
-    // few row tiles: split N over several workgroups per tile until the launch has >= 3 rounds of work for its slots
-    const int tiles = B * (HW / 8), nch = N / LCH, slots = 256 * 2;
-    int nsplit = 1;
-    while (tiles * nsplit < 3 * slots && nsplit * 2 <= nch && nch / (nsplit * 2) >= 5) nsplit *= 2;
-    p.nsplit = nsplit; p.cpp = (nch + nsplit - 1) / nsplit; p.ntiles = tiles;
-    const dim3 grid((unsigned)((tiles + 7) / 8 * 8 * nsplit));
+    p.ntiles = B * (HW / 8);
+    const XsSplit sp = xs_split_n(p.ntiles, N / LCH, 256 * 2);
+    p.nsplit = sp.nsplit; p.cpp = sp.cpp;
+    const dim3 grid = sp.grid;
     hipStream_t stream = (hipStream_t)stream_;
     if (C == FD) return residual ? launch_gn_silu_tconv<1, true>(p, grid, stream) : launch_gn_silu_tconv<1, false>(p, grid, stream);
     return residual ? launch_gn_silu_tconv<2, true>(p, grid, stream) : launch_gn_silu_tconv<2, false>(p, grid, stream);

@@ -506,12 +506,6 @@ def ln_qkv_temporal_attn(x, ln, pw_qkv, out, *, B, T, HW, scale, ln_eps=1e-5):
     return out
 
 
-def ln_qkv_temporal_attn320(x, ln, pw_qkv, out, *, B, T, HW, scale, ln_eps=1e-5):
-    if pw_qkv.K != 320:
-        raise ValueError("ln_qkv_temporal_attn320: dim 320 (qkv weight [960, 320], no bias), T = 16, HW % 8 == 0")
-    return ln_qkv_temporal_attn(x, ln, pw_qkv, out, B=B, T=T, HW=HW, scale=scale, ln_eps=ln_eps)
-
-
 def gn_silu_tconv3(x, gamma, beta, stats, pw, out, *, B, T, HW, groups=32, residual=None):
     """out = tconv3(silu(GroupNorm(x))) (+ residual) for 320 / 640 input channels, statistics from groupnorm_stats over the
     clips (n_inst = B, rows_per_inst = T * HW); pw = PackedWeight.tconv3; rows ordered (clip, frame, position)."""

@@ -53,7 +53,7 @@ Bc, T, HW = 2, 16, M // 32
 pwq = ops.PackedWeight.linear(torch.randn(960, 320, generator=g) * 320 ** -0.5, None, DEV)
 qkv = torch.empty(M, 960, dtype=torch.bfloat16, device=DEV); att = torch.empty(M, 320, dtype=torch.bfloat16, device=DEV)
 def three(): ops.ln_linear(h, pwq, qkv, ln=(gam, bet)); ops.temporal_attn(qkv, att, B=Bc, T=T, HW=HW, heads=5, scale=0.125)
-def fusedta(): ops.ln_qkv_temporal_attn320(h, (gam, bet), pwq, att, B=Bc, T=T, HW=HW, scale=0.125)
+def fusedta(): ops.ln_qkv_temporal_attn(h, (gam, bet), pwq, att, B=Bc, T=T, HW=HW, scale=0.125)
 for name, fn in (("ln_qkv+tattn", three), ("fused", fusedta), ("ln_qkv+tattn", three), ("fused", fusedta)):
     for _ in range(2): fn()
     torch.cuda.synchronize()

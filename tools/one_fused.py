@@ -33,7 +33,7 @@ elif which == "linres":
 elif which == "tattn":
     pwq = ops.PackedWeight.linear(torch.randn(960, 320, generator=g) * 320 ** -0.5, None, DEV)
     o = torch.empty_like(h)
-    fn = lambda: ops.ln_qkv_temporal_attn320(h, (gam, bet), pwq, o, B=Bc, T=T, HW=HW, scale=0.125)
+    fn = lambda: ops.ln_qkv_temporal_attn(h, (gam, bet), pwq, o, B=Bc, T=T, HW=HW, scale=0.125)
 elif which == "tattn640":                     # level 1: dim 640, M / 4 rows
     M4 = M // 4
     h6 = torch.randn(M4, 640, device=DEV).to(torch.bfloat16)
