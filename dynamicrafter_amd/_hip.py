@@ -116,7 +116,11 @@ SIGNATURES = {
     "dc_jpeg_dct_quant": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "dc_jpeg_entropy": (_I, [_P, _P, _P, _I, _I, _I, _I, _L, _P]),
     "dc_jpeg_pack": (_I, [_P, _P, _P, _P, _P, _I, _I, _L, _L, _P]),
-    "dc_prep_resize_h": (_I, [_P, _P, _P, _P, _P] + [_I] * 8 + [_P]),
+    "dc_gif_histogram": (_I, [_P, _P, _I, _I, _I, _P]),
+    "dc_gif_map": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
+    "dc_gif_lzw": (_I, [_P, _P, _P, _I, _I, _I, _L, _P]),
+    "dc_gif_pack": (_I, [_P, _P, _P, _P, _P, _I, _I, _L, _L, _P]),
+    "dc_prep_resize_h":(_I, [_P, _P, _P, _P, _P] + [_I] * 8 + [_P]),
     "dc_prep_finish": (_I, [_P, _P, _P, _P, _P] + [_I] * 15 + [_P]),
     "dc_mask_blend": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _L, _L, _I, _P]),
     "dc_advance_counter": (_I, [_P, _P]),

@@ -974,6 +974,90 @@ def jpeg_pack(scratch, seg_len, seg_off, out, frame_len, *, T, segs_per_frame, s
     return out
 
 
+# ---------------------------------------------------------------------------------------------- animated GIF (csrc/gif.hip)
+GIF_HIST_BINS = 32768                           # DC_GIF_HIST_BINS of include/dcrafter_hip.h
+GIF_CLEAR_INTERVAL = 3838                       # DC_GIF_CLEAR_INTERVAL: data codes in front of a Clear inside a chunk
+GIF_CHUNK = 8192                                # pixels per independently coded chunk (utils/save_video.py's default)
+
+
+def gif_chunk_max_bytes(n):
+    """DC_GIF_CHUNK_MAX_BYTES(n): the worst-case code string of a chunk of n pixels, in whole 32-bit words. n data codes, n // 3838
+    Clears inside the chunk and one terminator, 12 bits each."""
+    return (12 * (n + n // GIF_CLEAR_INTERVAL + 1) + 31) // 32 * 4
+
+
+def gif_frame_max_bytes(hw, chunk):
+    """The worst-case image data of one frame as dc_gif_pack writes it: the leading Clear and every chunk's worst case, in
+    sub-blocks of 255 bytes with their length bytes, and the closing 00."""
+    full, rest = divmod(hw, chunk)
+    bits = 9 + full * 12 * (chunk + chunk // GIF_CLEAR_INTERVAL + 1) + (12 * (rest + rest // GIF_CLEAR_INTERVAL + 1) if rest else 0)
+    nbytes = (bits + 7) // 8
+    return nbytes + (nbytes + 254) // 255 + 1
+
+
+def gif_histogram(frames, hist):
+    """frames uint8 [T, H, W, 3] -> hist uint32-as-int32 [32768]: pixels per bin (r>>3)<<10 | (g>>3)<<5 | (b>>3). The launch
+    clears hist itself."""
+    _flat(frames, torch.uint8, "frames"); _flat(hist, torch.int32, "hist")
+    if frames.dim() != 4 or frames.shape[3] != 3:
+        raise ValueError(f"gif_histogram: frames [T, H, W, 3] expected, got {tuple(frames.shape)}")
+    T, H, W, _ = frames.shape
+    if min(T, H, W) < 1 or T * H * W > 0xFFFFFFFF:
+        raise ValueError(f"gif_histogram: frames of {H} x {W} x {T}")
+    _need(hist, GIF_HIST_BINS, "hist")
+    _launch("gif_histogram(2 kernels)", 0.0, float(frames.numel()), _hip.lib().dc_gif_histogram, _ptr(frames), _ptr(hist), T, H, W,
+            stream_ptr())
+    return hist
+
+
+def gif_map(frames, palette, idx, *, n, dither=0):
+    """frames uint8 [T, H, W, 3] + palette uint8 [>= n, 3] -> idx uint8 [T, H, W]: ordered dither of amplitude `dither` (0..64),
+    then the nearest of the first n palette entries (ties to the lowest index)."""
+    _flat(frames, torch.uint8, "frames"); _flat(palette, torch.uint8, "palette"); _flat(idx, torch.uint8, "idx")
+    if frames.dim() != 4 or frames.shape[3] != 3:
+        raise ValueError(f"gif_map: frames [T, H, W, 3] expected, got {tuple(frames.shape)}")
+    T, H, W, _ = frames.shape
+    if min(T, H, W) < 1 or not 1 <= n <= 256 or not 0 <= dither <= 64:
+        raise ValueError(f"gif_map: frames of {H} x {W} x {T}, n {n}, dither {dither}")
+    _need(palette, 3 * n, "palette"); _need(idx, T * H * W, "idx")
+    _launch("gif_map", 8.0 * n * T * H * W, 4.0 * T * H * W, _hip.lib().dc_gif_map, _ptr(frames), _ptr(palette), _ptr(idx), T, H, W,
+            int(n), int(dither), stream_ptr())
+    return idx
+
+
+def gif_lzw(idx, scratch, chunk_bits, *, T, hw, chunk, stride):
+    """idx uint8 [T, hw] -> scratch uint8 [n_chunks, stride], chunk_bits int32 [n_chunks] (lengths in bits);
+    n_chunks = T ceil(hw / chunk)."""
+    _flat(idx, torch.uint8, "idx"); _flat(scratch, torch.uint8, "scratch"); _flat(chunk_bits, torch.int32, "chunk_bits")
+    if min(T, hw, chunk) < 1:
+        raise ValueError(f"gif_lzw: T {T}, hw {hw}, chunk {chunk}")
+    n_chunks = T * ((hw + chunk - 1) // chunk)
+    if stride % 4 or stride < gif_chunk_max_bytes(min(chunk, hw)):
+        raise ValueError(f"gif_lzw: stride {stride} is no multiple of 4 or below the worst case of {min(chunk, hw)} pixels")
+    if scratch.data_ptr() % 4:
+        raise ValueError("gif_lzw: scratch must be 4-byte aligned")
+    _need(idx, T * hw, "idx"); _need(scratch, n_chunks * stride, "scratch"); _need(chunk_bits, n_chunks, "chunk_bits")
+    _launch("gif_lzw", 0.0, float(T * hw), _hip.lib().dc_gif_lzw, _ptr(idx), _ptr(scratch), _ptr(chunk_bits), T, hw, chunk, stride,
+            stream_ptr())
+    return n_chunks
+
+
+def gif_pack(scratch, chunk_bits, chunk_off, out, frame_len, *, T, chunks_per_frame, stride, frame_stride):
+    """scratch [T chunks_per_frame, stride] + chunk_bits -> out uint8 [T, frame_stride] (a frame's sub-blocked image data behind a
+    leading Clear), frame_len int32 [T]; chunk_off int32 [T chunks_per_frame] is workspace."""
+    _flat(scratch, torch.uint8, "scratch"); _flat(out, torch.uint8, "out")
+    for t, name in ((chunk_bits, "chunk_bits"), (chunk_off, "chunk_off"), (frame_len, "frame_len")):
+        _flat(t, torch.int32, name)
+    if min(T, chunks_per_frame, stride, frame_stride) < 1 or T > 65535 or 9 + chunks_per_frame * stride * 8 > 0x7FFFFFFF:
+        raise ValueError(f"gif_pack: T {T}, chunks_per_frame {chunks_per_frame}, stride {stride}, frame_stride {frame_stride}")
+    n = T * chunks_per_frame
+    _need(scratch, n * stride, "scratch"); _need(chunk_bits, n, "chunk_bits"); _need(chunk_off, n, "chunk_off")
+    _need(out, T * frame_stride, "out"); _need(frame_len, T, "frame_len")
+    _launch("gif_pack(2 kernels)", 0.0, 0.0, _hip.lib().dc_gif_pack, _ptr(scratch), _ptr(chunk_bits), _ptr(chunk_off), _ptr(out),
+            _ptr(frame_len), T, chunks_per_frame, stride, frame_stride, stream_ptr())
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- image -> clip (csrc/preprocess.hip)
 RESIZE_PRECISION_BITS = 22                      # Pillow's PRECISION_BITS for 8-bit channels (32 - 8 - 2)
 

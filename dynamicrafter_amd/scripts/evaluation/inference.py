@@ -338,7 +338,8 @@ def load_data_prompts(data_dir, video_size=(256, 256), video_frames=16, interp=F
 def run_inference(args, gpu_num, gpu_no, device=None):
     """inference.py:316-380 for the rank slice `gpu_no` of `gpu_num` of the prompts, on device `gpu_no` as in the reference
     (`device`: another index, for a rank whose local device number differs). Clips go to <savedir>/samples_separate as
-    <image stem>_sample<i>.png (APNG) or .avi (`--container avi`); returns the paths written."""
+    <image stem>_sample<i>.png (APNG), .avi (`--container avi`) or .gif (`--container gif`, no dither); returns the paths
+    written."""
     import yaml
     from ... import parallel
     from ...utils.save_video import save_results_seperate
@@ -430,7 +431,8 @@ def get_parser():
     parser.add_argument("--interp", action="store_true", default=False, help="generate generative frame interpolation or not")
     # not in the reference
     parser.add_argument("--sampler", type=str, default="ddim", choices=("ddim",) + tuple(DPM_SOLVERS), help="sampler")
-    parser.add_argument("--container", type=str, default="apng", choices=("apng", "avi"), help="APNG (lossless) or Motion-JPEG AVI")
+    parser.add_argument("--container", type=str, default="apng", choices=("apng", "avi", "gif"),
+                        help="APNG (lossless), Motion-JPEG AVI or animated GIF (256 colours)")
     parser.add_argument("--quality", type=int, default=90, help="JPEG quality of --container avi")
     parser.add_argument("--num_frames", type=int, default=None, help="clip length in latent frames; above the model's "
                         "temporal_length the sampler denoises overlapping windows")

@@ -12,8 +12,15 @@ reference's stems; only the extension changes (.png instead of .mp4).
 (T.81 SOF0, YCbCr 4:2:0, Annex K tables scaled by `quality` as libjpeg does, restart intervals) by three HIP launches on
 the uint8 frames where they lie (csrc/jpeg.hip: coefficients, entropy coding of one restart segment per wave, pack); only the
 packed scans travel to the host, which adds the JFIF headers and the RIFF structure.
+
+`container="gif"` writes an animated GIF89a, the format the reference's gallery is shared in: one global colour table of up to
+256 entries for the whole clip (built on the host from a 15-bit histogram the GPU counts), every pixel mapped to its nearest
+entry, optionally behind an ordered dither, and LZW-coded in independent chunks (csrc/gif.hip: histogram, map, LZW of one chunk
+per wave, pack); only the packed image data travels to the host. A GIF frame lasts a whole number of centiseconds, at least 2:
+the file plays at 100 / delay frames per second, delay = max(2, floor(100 / fps + 0.5)), not at `fps` (8 -> 13 cs = 7.69 fps).
 """
 import ctypes as C
+import math
 import os
 import struct
 import zlib
@@ -251,32 +258,180 @@ def write_avi_mjpeg(path, jpeg_frames, width, height, fps):
     return path
 
 
-def _write_clip(stem, grid, fps, container, quality):
-    """grid uint8 [t, h, w, c] on the GPU -> <stem>.png (APNG) or <stem>.avi (Motion-JPEG)."""
+# ---------------------------------------------------------------------------------------------- animated GIF
+_GIF_SCRATCH_BYTES = 256 << 20           # LZW scratch per batch of frames (worst-case sized rows)
+
+
+def gif_palette(hist):
+    """hist: 32768 pixel counts over the bins (r>>3)<<10 | (g>>3)<<5 | (b>>3) (numpy or tensor, int32 bit patterns are read as
+    uint32) -> palette uint8 [n <= 256, 3]. A deterministic box-splitting quantiser on the occupied cells of the 32^3 grid with
+    count-weighted statistics (cell centres 8 v + 4): the box with the largest weighted sum of squared distances to its mean is
+    split by the axis-aligned cut that leaves the least such sum in the two halves (Wu's criterion, evaluated from 32-bin
+    marginal sums of the box; ties go to the lowest axis, then the lowest cut), until there are 256 boxes or every box is one
+    cell. An entry is the rounded weighted mean of its box; two boxes lie on different sides of a cut, so their entries differ
+    by at least 8 in that channel. A clip with at most 256 occupied cells gets exactly their centres. Pure numpy."""
+    h = hist.detach().cpu().numpy() if isinstance(hist, torch.Tensor) else np.asarray(hist)
+    if h.dtype == np.int32:
+        h = h.view(np.uint32)
+    h = h.reshape(-1).astype(np.int64)
+    if h.size != ops.GIF_HIST_BINS or (h < 0).any() or not h.any():
+        raise ValueError("gif_palette: 32768 non-negative counts expected, at least one of them above 0")
+    occ = np.flatnonzero(h)
+    w = h[occ].astype(np.float64)
+    g = np.stack([occ >> 10, (occ >> 5) & 31, occ & 31], 1)                     # grid coordinates 0..31, int64 [m, 3]
+    wg = w[:, None] * g                                                         # exact: counts < 2^32, coordinates < 2^5
+    wq = (wg * g).sum(1)
+
+    def stats(ix):
+        W, S = w[ix].sum(), wg[ix].sum(0)
+        return W, S, (0.0 if ix.size == 1 else max(wq[ix].sum() - float(S @ S) / W, 0.0))
+
+    boxes = [np.arange(occ.size)]
+    st = [stats(boxes[0])]
+    while len(boxes) < 256:
+        b = max(range(len(boxes)), key=lambda i: (st[i][2], -i))                # the largest sum; the earliest box on a tie
+        W, S, sse = st[b]
+        ix = boxes[b]
+        if ix.size < 2 or sse <= 0.0:
+            break
+        score = np.full((3, 31), -1.0)
+        gb, wb, wgb = g[ix], w[ix], wg[ix]
+        for a in range(3):
+            wl = np.cumsum(np.bincount(gb[:, a], wb, 32))[:31]                  # weight at coordinate <= c, c = 0..30
+            sl = np.stack([np.cumsum(np.bincount(gb[:, a], wgb[:, k], 32))[:31] for k in range(3)], 1)
+            ok = (wl > 0) & (wl < W)
+            wr, sr = W - wl, S[None] - sl
+            with np.errstate(divide="ignore", invalid="ignore"):
+                sc = (sl * sl).sum(1) / wl + (sr * sr).sum(1) / wr
+            score[a, ok] = sc[ok]
+        a, c = divmod(int(np.argmax(score)), 31)
+        left = gb[:, a] <= c
+        boxes[b], st[b] = ix[left], stats(ix[left])
+        boxes.append(ix[~left])
+        st.append(stats(ix[~left]))
+    pal = np.array([np.floor(8.0 * S / W + 4.0 + 0.5) for W, S, _ in st])
+    return np.clip(pal, 0, 255).astype(np.uint8)
+
+
+def gif_delay(fps):
+    """Centiseconds per frame: max(2, floor(100 / fps + 0.5)). Players treat delays below 2 as 10, so 2 is the shortest."""
+    if not fps > 0:
+        raise ValueError(f"fps must be positive, got {fps}")
+    return min(max(2, int(math.floor(100.0 / fps + 0.5))), 65535)
+
+
+def gif_file(width, height, palette, images, fps=8, loops=0):
+    """The GIF89a container around `images` (per frame: the sub-blocked LZW data behind the minimum code size byte, closed by
+    its 00 block): header, logical screen descriptor, the global colour table padded to 256 entries with zeros, a NETSCAPE2.0
+    loop extension (`loops` = 0 repeats forever), per frame a graphic control extension (disposal 1, gif_delay(fps)) and a
+    full-frame image descriptor without a local table, the trailer. Pure host code; returns bytes."""
+    pal = np.ascontiguousarray(palette, dtype=np.uint8)
+    images = [bytes(d) for d in images]
+    if not (1 <= width <= 65535 and 1 <= height <= 65535):
+        raise ValueError(f"gif_file: a GIF holds at most 65535 x 65535 pixels, got {width} x {height}")
+    if pal.ndim != 2 or pal.shape[1] != 3 or not 1 <= pal.shape[0] <= 256:
+        raise ValueError(f"gif_file: a palette uint8 [1..256, 3] expected, got {pal.shape}")
+    if not images or not 0 <= int(loops) <= 65535:
+        raise ValueError(f"gif_file: {len(images)} frames, loops {loops}")
+    delay = gif_delay(fps)
+    out = [b"GIF89a", struct.pack("<HHBBB", width, height, 0xF7, 0, 0), pal.tobytes() + bytes(3 * (256 - pal.shape[0])),
+           b"\x21\xff\x0bNETSCAPE2.0\x03\x01" + struct.pack("<H", int(loops)) + b"\x00"]
+    for d in images:
+        out += [b"\x21\xf9\x04" + struct.pack("<BHB", 0x04, delay, 0) + b"\x00",
+                b"\x2c" + struct.pack("<HHHHB", 0, 0, width, height, 0), b"\x08", d]
+    out.append(b"\x3b")
+    return b"".join(out)
+
+
+def encode_gif_frames(frames_u8, dither=0, chunk=None):
+    """frames_u8: uint8 [t, h, w, 3] on the GPU (what frames_to_uint8 returns) -> (palette uint8 [n <= 256, 3] (numpy), list of
+    t image data byte strings for gif_file). `dither` in 0..64 is the amplitude of the ordered (Bayer 8x8) dither in front of the
+    nearest-colour search; 0 = none: the smallest file, smooth gradients band. `chunk` = pixels per independently LZW-coded chunk
+    (default ops.GIF_CHUNK). One histogram launch and one device-to-host copy of 128 KiB for the palette, then three launches per
+    batch of frames and one copy of the packed data."""
+    if not isinstance(frames_u8, torch.Tensor) or not frames_u8.is_cuda:
+        raise RuntimeError("encode_gif_frames runs on the HIP path only (there is no CPU fallback)")
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4:
+        raise ValueError(f"encode_gif_frames: uint8 [t, h, w, 3] expected, got {frames_u8.dtype} {tuple(frames_u8.shape)}")
+    if frames_u8.shape[3] != 3:
+        raise ValueError(f"encode_gif_frames: 3 channels expected, got {frames_u8.shape[3]} (APNG takes 1 and 4)")
+    f = frames_u8.contiguous()
+    t, h, w, _ = f.shape
+    if t < 1 or not (1 <= h <= 65535 and 1 <= w <= 65535):
+        raise ValueError(f"encode_gif_frames: frames of {h} x {w} x {t}")
+    if not 0 <= int(dither) <= 64:
+        raise ValueError(f"dither must be in 0..64, got {dither}")
+    hw = h * w
+    chunk = ops.GIF_CHUNK if chunk is None else int(chunk)
+    if chunk < 1:
+        raise ValueError(f"chunk must be at least 1 pixel, got {chunk}")
+    dev = f.device
+    hist = torch.empty(ops.GIF_HIST_BINS, dtype=torch.int32, device=dev)
+    ops.gif_histogram(f, hist)
+    palette = gif_palette(hist)
+    pal_dev = torch.from_numpy(palette).to(dev)
+    cpf = (hw + chunk - 1) // chunk
+    stride = ops.gif_chunk_max_bytes(min(chunk, hw))
+    frame_stride = ops.gif_frame_max_bytes(hw, chunk)
+    tb = max(1, min(t, _GIF_SCRATCH_BYTES // (cpf * stride)))             # frames per batch
+    idx = torch.empty(tb * hw, dtype=torch.uint8, device=dev)
+    scratch = torch.empty(tb * cpf * stride, dtype=torch.uint8, device=dev)
+    chunk_bits, chunk_off = (torch.empty(tb * cpf, dtype=torch.int32, device=dev) for _ in range(2))
+    frame_len = torch.empty(tb, dtype=torch.int32, device=dev)
+    out = torch.empty(tb * frame_stride, dtype=torch.uint8, device=dev)
+    images = []
+    for t0 in range(0, t, tb):
+        n = min(tb, t - t0)
+        ops.gif_map(f[t0:t0 + n], pal_dev, idx, n=palette.shape[0], dither=int(dither))
+        ops.gif_lzw(idx, scratch, chunk_bits, T=n, hw=hw, chunk=chunk, stride=stride)
+        ops.gif_pack(scratch, chunk_bits, chunk_off, out, frame_len, T=n, chunks_per_frame=cpf, stride=stride,
+                     frame_stride=frame_stride)
+        lens = frame_len[:n].cpu().tolist()
+        if max(lens) > frame_stride:
+            raise RuntimeError(f"encode_gif_frames: a frame of {max(lens)} bytes outgrew the worst case {frame_stride}")
+        host = out[:n * frame_stride].view(n, frame_stride)[:, :max(lens)].cpu().numpy()
+        images += [host[i, :lens[i]].tobytes() for i in range(n)]
+    return palette, images
+
+
+def write_gif(path, frames_u8, fps=8, loops=0, dither=0, chunk=None):
+    """frames_u8: uint8 [t, h, w, 3] on the GPU -> an animated GIF89a that plays at 100 / gif_delay(fps) frames per second."""
+    palette, images = encode_gif_frames(frames_u8, dither=dither, chunk=chunk)
+    data = gif_file(frames_u8.shape[2], frames_u8.shape[1], palette, images, fps=fps, loops=loops)
+    os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
+    with open(path, "wb") as fh:
+        fh.write(data)
+    return path
+
+
+def _write_clip(stem, grid, fps, container, quality, dither=0):
+    """grid uint8 [t, h, w, c] on the GPU -> <stem>.png (APNG), <stem>.avi (Motion-JPEG) or <stem>.gif."""
     if container == "apng":
         return write_apng(stem + ".png", grid, fps=fps)
     if container == "avi":
         return write_avi_mjpeg(stem + ".avi", encode_jpeg_frames(grid, quality=quality), grid.shape[2], grid.shape[1], fps)
-    raise ValueError(f"container must be 'apng' or 'avi', got {container!r}")
+    if container == "gif":
+        return write_gif(stem + ".gif", grid, fps=fps, dither=dither)
+    raise ValueError(f"container must be 'apng', 'avi' or 'gif', got {container!r}")
 
 
 # ---------------------------------------------------------------------------------------------- reference-named entry points
-def save_results(prompt, samples, filename, fakedir, fps=8, loop=False, container="apng", quality=90):
+def save_results(prompt, samples, filename, fakedir, fps=8, loop=False, container="apng", quality=90, dither=0):
     """inference.py:115-137: the batch as ONE clip, its n samples side by side. samples [n, c, t, h, w]. `container`: "apng"
-    (default, lossless) or "avi" (Motion-JPEG at JPEG `quality`)."""
+    (default, lossless), "avi" (Motion-JPEG at JPEG `quality`) or "gif" (256 colours, ordered dither of amplitude `dither`)."""
     video = samples[:, :, :-1] if loop else samples            # loop mode drops the duplicated last frame
     grid = frames_to_uint8(video)
-    return _write_clip(os.path.join(fakedir, filename.split(".")[0]), grid, fps, container, quality)
+    return _write_clip(os.path.join(fakedir, filename.split(".")[0]), grid, fps, container, quality, dither)
 
 
-def save_results_seperate(prompt, samples, filename, fakedir, fps=10, loop=False, container="apng", quality=90):
+def save_results_seperate(prompt, samples, filename, fakedir, fps=10, loop=False, container="apng", quality=90, dither=0):
     """inference.py:140-162: one clip file per sample, under `samples_separate` (name kept as the reference spells it)."""
     video = samples[:, :, :-1] if loop else samples
     out = []
     d = fakedir.replace("samples", "samples_separate")
     for i in range(video.shape[0]):
         grid = frames_to_uint8(video[i:i + 1])
-        out.append(_write_clip(os.path.join(d, f"{filename.split('.')[0]}_sample{i}"), grid, fps, container, quality))
+        out.append(_write_clip(os.path.join(d, f"{filename.split('.')[0]}_sample{i}"), grid, fps, container, quality, dither))
     return out
 
 

@@ -457,6 +457,57 @@ int dc_jpeg_entropy(const int16_t* coef, uint8_t* scratch, int32_t* seg_len, int
 int dc_jpeg_pack(const uint8_t* scratch, const int32_t* seg_len, int32_t* seg_off, uint8_t* out, int32_t* frame_len, int T,
                  int segs_per_frame, int64_t stride, int64_t frame_stride, void* stream);
 
+/* ---- animated GIF (GIF89a, one global colour table of up to 256 entries, LZW minimum code size 8) ----
+ * Together the four entries stand where the reference hands its uint8 frames to a video encoder
+ * (torchvision.io.write_video: utils/save_video.py:27-43, scripts/evaluation/inference.py:115-162) and where its guidance
+ * pipeline saves a GIF preview through Pillow (guidance_pipeline.py:647-660: duration 125 ms, loop 0); the host builds the
+ * palette from the histogram and writes the container
+ * (dynamicrafter_amd/utils/save_video.py). None of them allocates or synchronises; all check their arguments before any launch.
+ * A frame's raster of hw = H*W indices is cut into chunks of `chunk` pixels (the last may be shorter, chunks may cross rows):
+ * chunks_per_frame = ceil(hw / chunk). Every chunk is LZW-coded from the reset state, so chunks are independent. */
+
+#define DC_GIF_HIST_BINS 32768
+/* Upper bound of one chunk's code string: every one of its n pixels emits at most one data code of at most 12 bits; a Clear
+ * inside the chunk needs 3838 data codes (258..4095 assigned) in front of it, so there are at most n / 3838 of them, 12 bits each;
+ * one terminator of at most 12 bits. In bytes it is rounded up to whole 32-bit words (the coder stores aligned words). */
+#define DC_GIF_CLEAR_INTERVAL 3838
+#define DC_GIF_CHUNK_MAX_BITS(n) (12LL * ((n) + (n) / DC_GIF_CLEAR_INTERVAL + 1))
+#define DC_GIF_CHUNK_MAX_BYTES(n) ((DC_GIF_CHUNK_MAX_BITS(n) + 31) / 32 * 4)
+
+/* frames[T][H][W][3] uint8 -> hist[32768] uint32: the number of pixels of the whole clip in each bin
+ * (r>>3)<<10 | (g>>3)<<5 | (b>>3). The entry clears hist itself; integer atomics, so the result does not depend on order.
+ * T*H*W < 2^32.
+ * replaces guidance_pipeline.py:647-660 (the colour statistics of Pillow's quantiser) */
+int dc_gif_histogram(const uint8_t* frames, uint32_t* hist, int T, int H, int W, void* stream);
+
+/* frames[T][H][W][3] uint8 + palette[n][3] uint8 (device, 1 <= n <= 256) -> idx[T][H][W] uint8. All integer:
+ *   d = floor((2 B[y&7][x&7] - 63) * dither / 128), B the 8x8 Bayer matrix with values 0..63 (B[0][0..7] = 0 32 8 40 2 34 10 42,
+ *   B[1][0] = 48), dither in 0..64; c' = clamp(c + d, 0, 255) per channel; idx = the entry among the first n with the least
+ *   dr^2 + dg^2 + db^2 to c', ties to the lowest index. d depends on the position only, not on the frame: a static pixel maps
+ *   to the same index in every frame. Exact search, the palette in LDS.
+ * replaces guidance_pipeline.py:647-660 (Pillow's RGB -> P conversion on save) */
+int dc_gif_map(const uint8_t* frames, const uint8_t* palette, uint8_t* idx, int T, int H, int W, int n, int dither, void* stream);
+
+/* idx[T][hw] -> one LZW code string per chunk, codes packed LSB first: scratch[n_chunks][stride] (bytes; the last byte of a
+ * string padded with zero bits, nothing written behind it), chunk_bits[n_chunks] = its length in BITS,
+ * n_chunks = T * ceil(hw / chunk), frames in order. A string starts in the reset state (width 9, next code 258) and holds the
+ * chunk's data codes; after code 4095 has been assigned it holds a Clear at 12 bits and starts over; it ends with a Clear if
+ * another chunk of the frame follows, with EOI if not, written at the width a decoder has after adding the entry that follows
+ * the last data code. The leading Clear of a frame is not part of any string (dc_gif_pack writes it).
+ * scratch 4-byte aligned (else DC_ERR_ARG); stride a multiple of 4 and >= DC_GIF_CHUNK_MAX_BYTES(min(chunk, hw)), else
+ * DC_ERR_SHAPE.
+ * replaces guidance_pipeline.py:647-660 (Pillow's GIF encoder: the LZW stage) */
+int dc_gif_lzw(const uint8_t* idx, uint8_t* scratch, int32_t* chunk_bits, int T, int hw, int chunk, int64_t stride, void* stream);
+
+/* Exclusive scan of each frame's chunk bit lengths behind a 9-bit leading Clear into chunk_off[n_chunks] (workspace, bit
+ * offsets), then a shift-merge gather of the strings at their bit offsets, the last byte padded with zero bits, wrapped into
+ * sub-blocks (a length byte, at most 255 data bytes) and closed by a 00 block: out[T][frame_stride] is what follows the LZW
+ * minimum code size byte of an image; frame_len[T] = its length. Bytes beyond frame_stride are not written: a frame_len above
+ * frame_stride tells the caller to pack again into wider rows. T <= 65535; chunks_per_frame * stride * 8 + 9 < 2^31.
+ * replaces guidance_pipeline.py:647-660 (Pillow's GIF encoder: the output stage) */
+int dc_gif_pack(const uint8_t* scratch, const int32_t* chunk_bits, int32_t* chunk_off, uint8_t* out, int32_t* frame_len, int T,
+                int chunks_per_frame, int64_t stride, int64_t frame_stride, void* stream);
+
 /* ---- image -> conditioning clip: Pillow's antialiased bilinear resize, centre crop / zero padding, ToTensor, Normalize ----
  * Together the two entries stand where the reference's loader runs torchvision's Resize(min(video_size)) ->
  * CenterCrop(video_size) -> ToTensor -> Normalize(0.5, 0.5) on a PIL image and repeats the result over the frames
