@@ -122,6 +122,8 @@ SIGNATURES = {
     "dc_gif_pack": (_I, [_P, _P, _P, _P, _P, _I, _I, _L, _L, _P]),
     "dc_prep_resize_h":(_I, [_P, _P, _P, _P, _P] + [_I] * 8 + [_P]),
     "dc_prep_finish": (_I, [_P, _P, _P, _P, _P] + [_I] * 15 + [_P]),
+    "dc_resize_f32_h": (_I, [_P, _P, _P, _P, _P] + [_I] * 10 + [_P]),
+    "dc_resize_f32_finish": (_I, [_P, _P, _P, _P, _P] + [_I] * 13 + [_P]),
     "dc_mask_blend": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _L, _L, _I, _P]),
     "dc_advance_counter": (_I, [_P, _P]),
     "dc_stream_create": (_I, [C.POINTER(_P)]),

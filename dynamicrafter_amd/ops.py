@@ -1165,6 +1165,205 @@ def prep_finish(src, clip, tab, *, axis, src_hw, origin, resized, offset, t0, nt
     return clip
 
 
+# ---------------------------------------------------------------------------------------------- float image resize (csrc/preprocess.hip)
+def resize_coeffs_f32(n_in, n_out, antialias):
+    """Bilinear resampling tables of one axis for fp32 images, on the host in float32 with ATen's operation order
+    (UpSampleKernel.cpp): k fp32 [n_out, ksize], xmin int32 [n_out], n int32 [n_out] (numpy). scale = n_in / n_out.
+    antialias=True: the window rule of _compute_indices_min_size_weights_aa with the triangle filter; the support is `scale` on a
+    downscale and 1 otherwise, the weights are summed tap by tap and normalised to sum 1.
+    antialias=False: interpolate's two taps (area_pixel_compute_source_index, guard_index_and_lambda): src = fma(scale, i + 0.5,
+    -0.5) clamped at 0, i0 = min(floor(src), n_in - 1), lambda = src - i0, weights (1 - lambda, lambda); at the right border,
+    where both taps are the last pixel, one tap of weight 1. The window rule with support 1 describes the same two taps, but
+    rounds the position at another place than ATen does, which shows from a few hundred pixels on (2^-24 * n_in in a weight)."""
+    import numpy as np
+    n_in, n_out = int(n_in), int(n_out)
+    if n_in < 1 or n_out < 1:
+        raise ValueError(f"resize_coeffs_f32: {n_in} -> {n_out}")
+    f = np.float32
+    scale = f(n_in) / f(n_out)
+    if not antialias:
+        # one rounding, as ATen's builds contract the expression into a fused multiply-add (the float64 product is exact)
+        src = np.maximum((np.float64(scale) * (np.arange(n_out, dtype=np.float64) + 0.5) - 0.5).astype(f), f(0.0))
+        i0 = np.minimum(src.astype(np.int64), n_in - 1)                        # src >= 0: truncation = floor
+        lam = np.minimum(np.maximum(src - i0.astype(f), f(0.0)), f(1.0))
+        two = i0 + 1 <= n_in - 1
+        w = np.zeros((n_out, 2), dtype=f)
+        w[:, 0] = np.where(two, f(1.0) - lam, f(1.0))
+        w[:, 1] = np.where(two, lam, f(0.0))
+        return w, i0.astype(np.int32), np.where(two, 2, 1).astype(np.int32)
+    aa = scale >= 1.0
+    support = scale if aa else f(1.0)
+    invscale = f(1.0) / scale if aa else f(1.0)
+    ksize = int(math.ceil(float(support))) * 2 + 1
+    center = scale * (np.arange(n_out, dtype=f) + f(0.5))
+    xmin = np.maximum((center - support + f(0.5)).astype(np.int64), 0)         # the cast truncates, as C's (int) does
+    xmax = np.minimum((center + support + f(0.5)).astype(np.int64), n_in)
+    n = xmax - xmin
+    w = np.zeros((n_out, ksize), dtype=f)
+    total = np.zeros(n_out, dtype=f)
+    for j in range(ksize):
+        a = np.abs((f(j) + xmin.astype(f) - center + f(0.5)) * invscale)
+        w[:, j] = np.where(j < n, np.maximum(f(0.0), f(1.0) - a), f(0.0))
+        total += w[:, j]
+    w = np.where((total != 0)[:, None], w / np.where(total != 0, total, f(1.0))[:, None], w).astype(f)
+    return w, xmin.astype(np.int32), n.astype(np.int32)
+
+
+class ResizeTablesF32:
+    """Device copy of resize_coeffs_f32(n_in, n_out, antialias) plus the host bounds the launch wrappers plan and check with
+    (the kernels trust the tables, as with ResizeTables)."""
+
+    __slots__ = ("n_in", "n_out", "antialias", "ksize", "k", "xmin", "n", "host_xmin", "host_n")
+
+    def __init__(self, n_in, n_out, antialias, device):
+        k, xmin, n = resize_coeffs_f32(n_in, n_out, antialias)
+        if (xmin < 0).any() or (n < 1).any() or (n > k.shape[1]).any() or (xmin.astype("int64") + n > n_in).any():
+            raise AssertionError(f"resize tables {n_in} -> {n_out}: a window leaves the input")
+        if (xmin[1:] < xmin[:-1]).any() or ((xmin + n)[1:] < (xmin + n)[:-1]).any():
+            raise AssertionError(f"resize tables {n_in} -> {n_out}: the windows do not advance with the output")
+        self.n_in, self.n_out, self.antialias, self.ksize = int(n_in), int(n_out), bool(antialias), int(k.shape[1])
+        self.host_xmin, self.host_n = xmin, n
+        self.k, self.xmin, self.n = (torch.from_numpy(a).to(device) for a in (k, xmin, n))
+
+    span = ResizeTables.span
+
+
+def _planes_f32(t, name):
+    _flat(t, torch.float32, name)
+    if t.dim() != 3 or min(t.shape) < 1:
+        raise ValueError(f"{name}: fp32 [C, H, W] expected, got {tuple(t.shape)}")
+    return tuple(t.shape)
+
+
+RESIZE_F32_TILE, RESIZE_F32_LDS_MAX = 256, 65536       # DC_RESIZE_F32_TILE, DC_RESIZE_F32_LDS_MAX (include/dcrafter_hip.h)
+
+
+def resize_f32_h_seg(tab, x0, cols):
+    """The `seg` argument of dc_resize_f32_h for the resized columns x0 .. x0 + cols - 1: the most source columns a tile of
+    RESIZE_F32_TILE outputs spans, or 0 (the direct form) when that and the tile's weights exceed RESIZE_F32_LDS_MAX bytes."""
+    import numpy as np
+    first = np.arange(x0, x0 + cols, RESIZE_F32_TILE)
+    last = np.minimum(first + RESIZE_F32_TILE - 1, x0 + cols - 1)
+    seg = int((tab.host_xmin[last].astype(np.int64) + tab.host_n[last] - tab.host_xmin[first]).max())
+    return seg if 4 * (seg + RESIZE_F32_TILE * tab.ksize) <= RESIZE_F32_LDS_MAX else 0
+
+
+def resize_f32_h(src, tmp, tab, *, y0, rows, x0, cols, staged=None):
+    """Horizontal pass of src fp32 [C, H, W] into tmp fp32 [C, rows, cols] (workspace of the caller): source rows
+    y0 .. y0 + rows - 1, resized columns x0 .. x0 + cols - 1 (dc_resize_f32_h). `staged`: through the LDS (True), straight from
+    global memory (False), or (None) through the LDS whenever a tile's source segment and weights fit it; the same bits."""
+    Cn, H, W = _planes_f32(src, "src")
+    _flat(tmp, torch.float32, "tmp")
+    if tab.n_in != W or tab.k.device != src.device or tmp.device != src.device:
+        raise ValueError(f"resize_f32_h: tables for width {tab.n_in} on {tab.k.device}, source width {W} on {src.device}")
+    if rows < 1 or cols < 1 or y0 < 0 or y0 + rows > H or x0 < 0 or x0 + cols > tab.n_out:
+        raise ValueError(f"resize_f32_h: rows {y0}+{rows} of {H}, columns {x0}+{cols} of {tab.n_out}")
+    _need(tmp, Cn * rows * cols, "tmp")
+    seg = resize_f32_h_seg(tab, x0, cols)
+    fits = seg > 0
+    if staged and not fits:
+        raise ValueError(f"resize_f32_h: a tile's source segment and its {tab.ksize}-tap weights are more than the LDS form takes")
+    if staged is False or not fits:
+        seg = 0
+    _launch("resize_f32_h", 0.0, 4.0 * Cn * (rows * W + rows * cols), _hip.lib().dc_resize_f32_h, _ptr(src), _ptr(tmp),
+            _ptr(tab.k), _ptr(tab.xmin), _ptr(tab.n), tab.ksize, Cn, H, W, tab.n_out, y0, rows, x0, cols, seg, stream_ptr())
+    return tmp
+
+
+def resize_f32_finish(src, out, tab, *, axis, src_hw, origin, resized, offset):
+    """The last pass (axis 0: none, 1: horizontal, 2: vertical; `tab` = its ResizeTablesF32 or None) + crop / 0.0 padding into
+    out fp32 [C, ch, cw] (dc_resize_f32_finish). src: fp32, C planes of `src_hw` pixels whose first is pixel `origin` = (y, x) of
+    its image; `resized` = (rh, rw); pixel (oy, ox) of out is the resized pixel (oy + offset[0], ox + offset[1])."""
+    _flat(src, torch.float32, "src")
+    Cn, ch, cw = _planes_f32(out, "out")
+    if out.device != src.device:
+        raise ValueError(f"resize_f32_finish: out on {out.device}, src on {src.device}")
+    (sh, sw), (sy0, sx0), (rh, rw), (yoff, xoff) = src_hw, origin, resized, offset
+    if min(sh, sw, rh, rw) < 1 or sy0 < 0 or sx0 < 0:
+        raise ValueError(f"resize_f32_finish: src {sh} x {sw} at {sy0}, {sx0}, resized {rh} x {rw}")
+    _need(src, Cn * sh * sw, "src")
+    if axis not in (0, 1, 2) or (tab is None) != (axis == 0):
+        raise ValueError(f"resize_f32_finish: axis {axis} with{'out' if tab is None else ''} tables")
+    ry0, ry1, rx0, rx1 = max(yoff, 0), min(ch + yoff, rh), max(xoff, 0), min(cw + xoff, rw)
+    if ry0 < ry1 and rx0 < rx1:
+        # along the axis it is addressed directly, src holds every resized pixel the crop keeps (the entry checks this too)
+        if (axis != 2 and (ry0 < sy0 or ry1 > sy0 + sh)) or (axis != 1 and (rx0 < sx0 or rx1 > sx0 + sw)):
+            raise ValueError(f"resize_f32_finish: the crop keeps rows {ry0} .. {ry1 - 1}, columns {rx0} .. {rx1 - 1}; src holds "
+                             f"{sh} x {sw} from ({sy0}, {sx0})")
+    if tab is not None:
+        if tab.k.device != src.device or tab.n_out != (rw if axis == 1 else rh):
+            raise ValueError(f"resize_f32_finish: tables {tab.n_in} -> {tab.n_out} on {tab.k.device} for a resized image of "
+                             f"{rh} x {rw}")
+        lo, hi, s0, sn = (rx0, rx1, sx0, sw) if axis == 1 else (ry0, ry1, sy0, sh)
+        if lo < hi:                             # the windows of every output the crop keeps lie inside src (the kernel trusts this)
+            first, count = tab.span(lo, hi)
+            if first < s0 or first + count > s0 + sn:
+                raise ValueError(f"resize_f32_finish: the pass reads inputs {first} .. {first + count - 1}, src holds {s0} .. "
+                                 f"{s0 + sn - 1}")
+    z = C.c_void_p(0)
+    _launch("resize_f32_finish", 0.0, 4.0 * Cn * (sh * sw + ch * cw), _hip.lib().dc_resize_f32_finish, _ptr(src), _ptr(out),
+            z if tab is None else _ptr(tab.k), z if tab is None else _ptr(tab.xmin), z if tab is None else _ptr(tab.n),
+            0 if tab is None else tab.ksize, axis, Cn, sh, sw, sy0, sx0, rh, rw, yoff, xoff, ch, cw, stream_ptr())
+    return out
+
+
+_RESIZE_TABLES_F32 = {}
+
+
+def _resize_tables_f32(n_in, n_out, antialias, device):
+    """Cached ResizeTablesF32 (an application resizes to one resolution; the last 16 are kept)."""
+    key = (int(n_in), int(n_out), bool(antialias), str(device))
+    tab = _RESIZE_TABLES_F32.pop(key, None)
+    if tab is None:
+        tab = ResizeTablesF32(n_in, n_out, antialias, device)
+    _RESIZE_TABLES_F32[key] = tab
+    while len(_RESIZE_TABLES_F32) > 16:
+        _RESIZE_TABLES_F32.pop(next(iter(_RESIZE_TABLES_F32)))
+    return tab
+
+
+def resize_f32(img, resized_hw, crop_hw=None, offset=(0, 0), antialias=True, out=None):
+    """img fp32 [C, H, W] on the device -> fp32 [C, ch, cw]: bilinear resize to `resized_hw` = (rh, rw) as
+    torch.nn.functional.interpolate(mode="bilinear", align_corners=False, antialias=antialias) does it, then the window of
+    `crop_hw` = (ch, cw) (default: the resized image) whose pixel (oy, ox) is the resized pixel (oy + offset[0], ox + offset[1]);
+    0.0 outside the resized image. One or two launches on the current stream (horizontal pass first, only the rows and columns
+    the crop keeps; a pass is left out when its axis keeps its size). Allocates the result unless `out` is given, and the
+    intermediate of a two-pass resize. HIP path only: a CPU tensor raises RuntimeError."""
+    if not isinstance(img, torch.Tensor) or not img.is_cuda or (out is not None and not out.is_cuda):
+        raise RuntimeError("resize_f32 runs on the HIP path only (there is no CPU fallback)")
+    Cn, H, W = _planes_f32(img, "img")
+    rh, rw = int(resized_hw[0]), int(resized_hw[1])
+    ch, cw = (rh, rw) if crop_hw is None else (int(crop_hw[0]), int(crop_hw[1]))
+    yoff, xoff = int(offset[0]), int(offset[1])
+    if min(rh, rw, ch, cw) < 1:
+        raise ValueError(f"resize_f32: resized {rh} x {rw}, crop {ch} x {cw}")
+    if out is None:
+        out = torch.empty((Cn, ch, cw), dtype=torch.float32, device=img.device)
+    elif tuple(out.shape) != (Cn, ch, cw) or out.dtype != torch.float32 or out.device != img.device or not out.is_contiguous():
+        raise ValueError(f"resize_f32: out must be contiguous fp32 [{Cn}, {ch}, {cw}] on {img.device}, got {out.dtype} "
+                         f"{tuple(out.shape)} on {out.device}")
+    with torch.cuda.device(img.device):
+        tab_x = _resize_tables_f32(W, rw, antialias, img.device) if rw != W else None
+        tab_y = _resize_tables_f32(H, rh, antialias, img.device) if rh != H else None
+        common = dict(resized=(rh, rw), offset=(yoff, xoff))
+        ry0, ry1, rx0, rx1 = max(yoff, 0), min(ch + yoff, rh), max(xoff, 0), min(cw + xoff, rw)
+        if ry0 >= ry1 or rx0 >= rx1:                                  # the window misses the image: all padding
+            resize_f32_finish(img, out, None, axis=0, src_hw=(H, W), origin=(0, 0), **common)
+        elif tab_x is not None and tab_y is not None:
+            y0, rows = tab_y.span(ry0, ry1)
+            cols = rx1 - rx0
+            tmp = torch.empty((Cn, rows, cols), dtype=torch.float32, device=img.device)
+            resize_f32_h(img, tmp, tab_x, y0=y0, rows=rows, x0=rx0, cols=cols)
+            resize_f32_finish(tmp, out, tab_y, axis=2, src_hw=(rows, cols), origin=(y0, rx0), **common)
+        elif tab_x is not None:
+            resize_f32_finish(img, out, tab_x, axis=1, src_hw=(H, W), origin=(0, 0), **common)
+        elif tab_y is not None:
+            resize_f32_finish(img, out, tab_y, axis=2, src_hw=(H, W), origin=(0, 0), **common)
+        else:
+            resize_f32_finish(img, out, None, axis=0, src_hw=(H, W), origin=(0, 0), **common)
+    return out
+
+
 class DeviceGraph:
     """hipGraph capture/replay of a block of dc_* calls issued on a private stream (runtime.hip)."""
 

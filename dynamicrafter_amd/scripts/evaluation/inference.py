@@ -204,6 +204,18 @@ def resize_geometry(h, w, video_size):
     return ResizeGeometry(rh, rw, pt, pb, pl, pr, top, left)
 
 
+def resize_center_crop_f32(img, video_size, antialias=True):
+    """torchvision's Resize(min(video_size)) -> CenterCrop(video_size) on a float tensor (scripts/gradio/i2v_test.py:39-42, 65;
+    dynamicrafter_pipeline.py:175-178, 286): img fp32 [C, H, W] on the device -> fp32 [C, h, w]. The sizes and offsets are
+    `resize_geometry`'s; the resize is interpolate(bilinear, antialias=True) as one or two HIP launches (ops.resize_f32), the
+    crop and its padding with 0.0 fused into the last. Not the uint8 path: `preprocess_image` reproduces Pillow on decoded
+    pixels, this reproduces what the reference's app classes do to an already normalised tensor."""
+    from ... import ops
+    g = resize_geometry(img.shape[-2], img.shape[-1], video_size)
+    return ops.resize_f32(img, (g.rh, g.rw), crop_hw=(int(video_size[0]), int(video_size[1])),
+                          offset=(g.top - g.pad_top, g.left - g.pad_left), antialias=antialias)
+
+
 class PreprocessPlan:
     """Everything `preprocess_launch` needs for images of one size: the geometry, the tables of the axes that change size (on
     the device) and the extent of the uint8 intermediate between the two passes. Building it uploads; launching does not."""

@@ -542,6 +542,49 @@ int dc_prep_finish(const uint8_t* src, float* clip, const int32_t* k, const int3
                    int sh, int sw, int sy0, int sx0, int rh, int rw, int yoff, int xoff, int ch, int cw, int T, int t0, int nt,
                    void* stream);
 
+/* ---- float image -> conditioning frame: bilinear resize of fp32 planes with optional antialias, crop / 0.0f padding ----
+ * The reference's programmatic entry points resize a float tensor already normalised to [-1, 1]: torchvision's Resize /
+ * CenterCrop on a tensor = torch.nn.functional.interpolate(mode="bilinear", align_corners=False, antialias=True) and a crop
+ * that pads with 0.0; cv2.resize(INTER_LINEAR) on float32 = the same with antialias=False. Per axis
+ *   out[xx] = sum_{i < n[xx]} in[xmin[xx] + i] * k[xx][i]                  (fp32, fma in tap order, per plane)
+ * horizontal pass first, an fp32 intermediate between the passes, a pass left out when its axis keeps its size.
+ * TABLES: k fp32 [out][ksize], xmin int32 [out], n int32 [out] are device memory built on the host
+ * (dynamicrafter_amd/ops.py resize_coeffs_f32, ATen's antialias window rule) and TRUSTED exactly as the uint8 tables above: the
+ * ops.py wrapper guarantees xmin + n <= in and n <= ksize, and a window that breaks this is cut to the operand inside the kernel.
+ * Images are planar fp32 [C][H][W], any C >= 1. Neither entry allocates or synchronises; both check their arguments before any
+ * launch. Not bit-compatible with the uint8 path (Pillow's fixed point) nor bit-for-bit with ATen (summation order): see
+ * DESIGN 4.8. */
+
+/* Horizontal pass of src fp32 [C][H][W] into the intermediate dst fp32 [C][rows][cols]: source rows y0 .. y0 + rows - 1 (the
+ * ones the vertical pass reads), resized columns x0 .. x0 + cols - 1 of out_w (the ones the crop keeps).
+ * seg = 0: every lane reads its window from global memory. seg > 0: a workgroup stages the source segment and the weights of
+ * DC_RESIZE_F32_TILE consecutive outputs (tiles count from x0) in the LDS; seg = the most source columns such a tile spans,
+ * max over tiles of xmin[last] + n[last] - xmin[first] (the caller knows the tables; xmin and xmin + n must not decrease; a
+ * window outside the staged segment is cut to it). DC_ERR_SHAPE if DC_RESIZE_F32_LDS_BYTES(seg, ksize) exceeds
+ * DC_RESIZE_F32_LDS_MAX: use seg = 0 then. Both forms sum in tap order and give the same bits.
+ * replaces scripts/gradio/i2v_test.py:39-42, 65; scripts/gradio/i2v_test_application.py:39-42, 65, 75;
+ * scripts/gradio/dynamicrafter_pipeline.py:281-288 (transforms.Resize on a tensor, horizontal pass) and
+ * scripts/evaluation/funcs.py:196 (cv2.resize INTER_LINEAR, horizontal pass) */
+#define DC_RESIZE_F32_TILE 256
+#define DC_RESIZE_F32_LDS_BYTES(seg, ksize) (4LL * ((long long)(seg) + (long long)DC_RESIZE_F32_TILE * (ksize)))
+#define DC_RESIZE_F32_LDS_MAX 65536
+int dc_resize_f32_h(const float* src, float* dst, const float* k, const int32_t* xmin, const int32_t* n, int ksize, int C, int H,
+                    int W, int out_w, int y0, int rows, int x0, int cols, int seg, void* stream);
+
+/* The last pass fused with crop and padding. src fp32 [C][sh][sw] is a part of an image whose pixel (sy0, sx0) is src's (0, 0)
+ * in every plane; the resized image is rh x rw; pixel (oy, ox) of out fp32 [C][ch][cw] is the resized pixel
+ * (oy + yoff, ox + xoff), or 0.0f where that lies outside the resized image.
+ *   axis 0: no pass (src is the resized image: a crop / pad copy);  k, kmin, kn may be NULL
+ *   axis 1: horizontal pass (src has the resized height; tables per resized column)
+ *   axis 2: vertical pass (src has the resized width: the source, or dc_resize_f32_h's intermediate; tables per resized row)
+ * DC_ERR_SHAPE unless src holds, along the axis it is addressed directly, every resized pixel the crop keeps.
+ * replaces scripts/gradio/i2v_test.py:39-42, 65; scripts/gradio/i2v_test_application.py:39-42, 65, 75;
+ * scripts/gradio/dynamicrafter_pipeline.py:281-288 (Resize's last pass and CenterCrop with its zero padding) and
+ * scripts/evaluation/funcs.py:196 (cv2.resize's last pass) */
+int dc_resize_f32_finish(const float* src, float* out, const float* k, const int32_t* kmin, const int32_t* kn, int ksize, int axis,
+                         int C, int sh, int sw, int sy0, int sx0, int rh, int rw, int yoff, int xoff, int ch, int cw,
+                         void* stream);
+
 /* Mask / x0 blend ahead of a DDIM step, in place on img [n] fp32: img = orig*mask + (1-mask)*img with
  * orig = x0 (clean != 0) or sqrt_acp_t[i]*x0 + sqrt_1macp_t[i]*qnoise (q_sample of x0 at the step's timestep);
  * i = step_index[0] (device counter; qnoise then starts at qnoise + i*noise_step_stride) or `index`.
