@@ -30,6 +30,18 @@ __device__ __forceinline__ uint32_t pack_bf2(float lo, float hi) {
     return __builtin_bit_cast(uint32_t, __builtin_convertvector(v, bf16x2_hw_t));
 }
 
+// a + b on packed bf16 pairs / on 8 packed values: each sum is formed in fp32 and rounded to bf16 once. The one spelling of the
+// residual add behind a bf16 result (tests/test_host_cpu.py::test_gemm_parts_are_spelled_once).
+__device__ __forceinline__ uint32_t add_bf2(uint32_t a, uint32_t b) {
+    return pack_bf2(__uint_as_float(a << 16) + __uint_as_float(b << 16),
+                    __uint_as_float(a & 0xffff0000u) + __uint_as_float(b & 0xffff0000u));
+}
+__device__ __forceinline__ u32x4_t add_bf8(u32x4_t a, const u32x4_t& b) {
+#pragma unroll
+    for (int e = 0; e < 4; ++e) a[e] = add_bf2(a[e], b[e]);
+    return a;
+}
+
 __device__ __forceinline__ bf16_t f2bf(float f) { return (bf16_t)(pack_bf2(f, 0.f) & 0xffffu); }
 
 __device__ __forceinline__ void unpack_bf8(const uint4& v, float* f) {

@@ -195,11 +195,10 @@ __device__ __forceinline__ void xs_load_chunk_rows(u32x4_t (&d)[2], const bf16_t
     for (int t = 0; t < 2; ++t)
         d[t] = *reinterpret_cast<const u32x4_t*>(R + rows.clamped(t * 16 + (lane >> 2)) * ldr + n0 + (lane & 3) * 8);
 }
+// (in place, pair by pair: through add_bf8's value form ff_geglu_fused320_kernel<false, false> needs 4 more registers)
 __device__ __forceinline__ void xs_add_bf16x8(u32x4_t& d, const u32x4_t& rr) {
 #pragma unroll
-    for (int e = 0; e < 4; ++e)
-        d[e] = pack_bf2(__uint_as_float(d[e] << 16) + __uint_as_float(rr[e] << 16),
-                        __uint_as_float(d[e] & 0xffff0000u) + __uint_as_float(rr[e] & 0xffff0000u));
+    for (int e = 0; e < 4; ++e) d[e] = add_bf2(d[e], rr[e]);
 }
 __device__ __forceinline__ void xs_add_bf16x4(float4& bv, uint2 rv) {
     bv.x += __uint_as_float(rv.x << 16); bv.y += __uint_as_float(rv.x & 0xffff0000u);
@@ -684,10 +683,8 @@ void ff_geglu_fused320_kernel(const FfParams p) {
                         const uint2 rr = *reinterpret_cast<const uint2*>(rrow + n);
                         const unsigned d0 = pack_bf2(acc[nb][4 * q] + bv.x, acc[nb][4 * q + 1] + bv.y);
                         const unsigned d1 = pack_bf2(acc[nb][4 * q + 2] + bv.z, acc[nb][4 * q + 3] + bv.w);
-                        fw[q >> 1][2 * (q & 1)] = pack_bf2(__uint_as_float(d0 << 16) + __uint_as_float(rr.x << 16),
-                                                          __uint_as_float(d0 & 0xffff0000u) + __uint_as_float(rr.x & 0xffff0000u));
-                        fw[q >> 1][2 * (q & 1) + 1] = pack_bf2(__uint_as_float(d1 << 16) + __uint_as_float(rr.y << 16),
-                                                              __uint_as_float(d1 & 0xffff0000u) + __uint_as_float(rr.y & 0xffff0000u));
+                        fw[q >> 1][2 * (q & 1)] = add_bf2(d0, rr.x);
+                        fw[q >> 1][2 * (q & 1) + 1] = add_bf2(d1, rr.y);
                     }
                     xf[2 * nb] = __builtin_bit_cast(bf16x8_t, fw[0]);
                     xf[2 * nb + 1] = __builtin_bit_cast(bf16x8_t, fw[1]);

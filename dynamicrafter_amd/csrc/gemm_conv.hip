@@ -19,6 +19,7 @@
 #include "dc_common.h"
 #include "dcrafter_hip.h"
 #include "lds_stage.h"
+#include "gemm_parts.h"
 #include <stdlib.h>
 
 namespace {
@@ -70,31 +71,21 @@ __global__ __launch_bounds__(NTHREADS) void gemm_conv_kernel(const DcGemmParams 
         if (MODE == 0) {
             if (ok) a_ptr[i] = p.A + (size_t)m * p.lda + chunk * 8;
         } else if (MODE == 1) {
-            const int ohw = p.OH * p.OW;
-            const int mm = ok ? m : 0;
-            const int n = mm / ohw;
-            const int rem = mm - n * ohw;
-            const int oy = rem / p.OW;
-            const int ox = rem - oy * p.OW;
+            int n, oy, ox;
+            conv_row(p, ok ? m : 0, n, oy, ox);
             if (ok) a_base[i] = n * p.IH * p.IW;
             a_y[i] = oy * p.stride - p.pad;
             a_x[i] = ox * p.stride - p.pad;
         } else {
             if (ok) a_ptr[i] = p.A + (size_t)m * p.lda + chunk * 8;
-            a_y[i] = ((ok ? m : 0) / p.HW) % p.T;   // frame index t
+            a_y[i] = tconv_frame(p, ok ? m : 0);
         }
     }
     // B rows handled by this thread
     const bf16_t* b_ptr[B_ITERS];
 #pragma unroll
     for (int i = 0; i < B_ITERS; ++i) {
-        const int r = srow + 32 * i;     // row inside the B tile
-        int wrow;
-        if (GEGLU) {
-            wrow = (r < BN / 2) ? (n0 + r) : ((p.N >> 1) + n0 + (r - BN / 2));
-        } else {
-            wrow = n0 + r;
-        }
+        const int wrow = gemm_wrow<BN, GEGLU>(p, n0, srow + 32 * i);
         b_ptr[i] = p.W + (size_t)wrow * p.K + chunk * 8;   // W is zero-padded to a multiple of the tile in N
     }
 
@@ -110,12 +101,9 @@ __global__ __launch_bounds__(NTHREADS) void gemm_conv_kernel(const DcGemmParams 
                 a_reg[i] = *reinterpret_cast<const u32x4_t*>(src);
             }
         } else if (MODE == 1) {
-            // K is ordered (64-channel slice, tap, channel): the 9 taps of one slice are consecutive K tiles, so
-            // taps 2..9 re-read (shifted) rows that the first tap just pulled into L2
-            const int cs = kt / 9;
-            const int tap = kt - cs * 9;
+            int cs, tap, dy, dx;
+            conv_ktile(kt, cs, tap, dy, dx);
             const int ci0 = cs * 64;
-            const int dy = tap / 3, dx = tap - dy * 3;
             const int eh = p.IH << p.ups, ew = p.IW << p.ups;
 #pragma unroll
             for (int i = 0; i < 4; ++i) {
@@ -126,8 +114,8 @@ __global__ __launch_bounds__(NTHREADS) void gemm_conv_kernel(const DcGemmParams 
                 a_reg[i] = *reinterpret_cast<const u32x4_t*>(src);
             }
         } else {
-            const int cs = kt / 3;
-            const int tap = kt - cs * 3;
+            int cs, tap;
+            tconv_ktile(kt, cs, tap);
             const int ci0 = cs * 64;
             const long long shift = (long long)(tap - 1) * p.HW * p.lda + ci0;
 #pragma unroll
@@ -239,42 +227,14 @@ __global__ __launch_bounds__(NTHREADS) void gemm_conv_kernel(const DcGemmParams 
             const int n = n0 + c;
             if (m >= p.M || n >= n_out) continue;
             float4 v = *reinterpret_cast<const float4*>(cs + r * CS_LD + c * 4);
-            if (p.bias) {
-                const float4 bv = *reinterpret_cast<const float4*>(p.bias + n);
-                v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
-            }
+            if (p.bias) ep_add4(v, p.bias + n);
             if constexpr (GEGLU) {
                 float4 g = *reinterpret_cast<const float4*>(cs + PLANE + r * CS_LD + c * 4);
-                if (p.bias) {
-                    const float4 bg = *reinterpret_cast<const float4*>(p.bias + (p.N >> 1) + n);
-                    g.x += bg.x; g.y += bg.y; g.z += bg.z; g.w += bg.w;
-                }
-                v.x *= DC_GELU(g.x); v.y *= DC_GELU(g.y); v.z *= DC_GELU(g.z); v.w *= DC_GELU(g.w);
+                if (p.bias) ep_add4(g, p.bias + (p.N >> 1) + n);
+                ep_geglu4(v, g);
             }
-            if (p.flags & DC_GEMM_GELU) { v.x = DC_GELU(v.x); v.y = DC_GELU(v.y); v.z = DC_GELU(v.z); v.w = DC_GELU(v.w); }
-            if (p.rowvec) {
-                const float4 rv = *reinterpret_cast<const float4*>(p.rowvec + (size_t)(m / p.rows_per_vec) * p.rowvec_ld + n);
-                v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;
-            }
-            if (p.alpha != 1.0f) { v.x *= p.alpha; v.y *= p.alpha; v.z *= p.alpha; v.w *= p.alpha; }
-            if (out_f32) {
-                *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.C) + (size_t)m * p.ldc + n) = v;
-            } else {
-                // bf16 rounding, then the residual add (as the reference adds two already-rounded tensors)
-                uint2 pk;
-                pk.x = pack_bf2(v.x, v.y);
-                pk.y = pack_bf2(v.z, v.w);
-                if (p.residual) {
-                    const uint2 rr = *reinterpret_cast<const uint2*>(p.residual + (size_t)m * p.ldr + n);
-                    const float a0 = __uint_as_float(pk.x << 16) + __uint_as_float(rr.x << 16);
-                    const float a1 = __uint_as_float(pk.x & 0xffff0000u) + __uint_as_float(rr.x & 0xffff0000u);
-                    const float a2 = __uint_as_float(pk.y << 16) + __uint_as_float(rr.y << 16);
-                    const float a3 = __uint_as_float(pk.y & 0xffff0000u) + __uint_as_float(rr.y & 0xffff0000u);
-                    pk.x = pack_bf2(a0, a1);
-                    pk.y = pack_bf2(a2, a3);
-                }
-                *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(p.C) + (size_t)m * p.ldc + n) = pk;
-            }
+            ep_tail4(v, p, m, n);
+            ep_store4(p, out_f32, m, n, v);
         }
     }
 }
@@ -534,25 +494,15 @@ __global__ __launch_bounds__(256, 2) void conv3x3_window128_kernel(const DcGemmP
             for (int c4 = 0; c4 < 4; ++c4) {
                 const int c = hf * 4 + c4;
                 float4 v = make_float4(acc[b][c][0], acc[b][c][1], acc[b][c][2], acc[b][c][3]);
-                if (p.bias) {
-                    const float4 bv = *reinterpret_cast<const float4*>(p.bias + 16 * c + 4 * lq);
-                    v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
-                }
-                uint2 pk;
-                pk.x = pack_bf2(v.x, v.y); pk.y = pack_bf2(v.z, v.w);
+                if (p.bias) ep_add4(v, p.bias + 16 * c + 4 * lq);
                 const int px = 16 * b + lj;                 // 8-byte slot (c4, lq) of the pixel's 128-byte row, chunk-swizzled
-                *reinterpret_cast<uint2*>(patch + nc_off(px, 2 * c4 + (lq >> 1)) + (lq & 1) * 8) = pk;
+                *reinterpret_cast<uint2*>(patch + nc_off(px, 2 * c4 + (lq >> 1)) + (lq & 1) * 8) = ep_pack4(v);
             }
 #pragma unroll
         for (int it = 0; it < 8; ++it) {
             const int px = it * 8 + rpx;
             u32x4_t d = *reinterpret_cast<const u32x4_t*>(patch + nc_off(px, rch));
-            if (p.residual) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    d[e] = pack_bf2(__uint_as_float(d[e] << 16) + __uint_as_float(rres[it][e] << 16),
-                                    __uint_as_float(d[e] & 0xffff0000u) + __uint_as_float(rres[it][e] & 0xffff0000u));
-            }
+            if (p.residual) d = add_bf8(d, rres[it]);
             if (tx0 + px < p.IW) *reinterpret_cast<u32x4_t*>(cbase + (row0 + px) * p.ldc + hf * 64 + rch * 8) = d;
         }
     }

@@ -15,6 +15,7 @@
 #include "dc_common.h"
 #include "dcrafter_hip.h"
 #include "lds_stage.h"
+#include "gemm_parts.h"
 #include <stdint.h>
 #include <stdlib.h>
 #include <type_traits>
@@ -97,35 +98,21 @@ __global__ __launch_bounds__(GNT) void gemm_conv_glds_kernel(const DcGemmParams 
         } else if (MODE == 1) {
             // conv3x3 without upsampling: pointer to tap (0,0) of this output row (may lie outside the image: only
             // dereferenced when its mask bit is set) + a 9-bit validity mask; the per-tap offset is wave-uniform
-            const int ohw = p.OH * p.OW;
-            const int mm = ok ? m : 0;
-            const int n = mm / ohw;
-            const int rem = mm - n * ohw;
-            const int oy = rem / p.OW;
-            const int ox = rem - oy * p.OW;
+            int n, oy, ox;
+            conv_row(p, ok ? m : 0, n, oy, ox);
             const int iy0 = oy * p.stride - p.pad, ix0 = ox * p.stride - p.pad;
-            int mask = 0;
-#pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                const int iy = iy0 + t / 3, ix = ix0 + t % 3;
-                if (ok && iy >= 0 && iy < p.IH && ix >= 0 && ix < p.IW) mask |= 1 << t;
-            }
-            a_base[j] = mask;
+            a_base[j] = conv_tap_mask(ok, iy0, ix0, p.IH, p.IW);
             a_ptr[j] = p.A + ((long long)n * p.IH * p.IW + (long long)iy0 * p.IW + ix0) * p.lda + chunk * 8;
         } else if (MODE == 3) {
-            const int ohw = p.OH * p.OW;
-            const int mm = ok ? m : 0;
-            const int n = mm / ohw;
-            const int rem = mm - n * ohw;
-            const int oy = rem / p.OW;
-            const int ox = rem - oy * p.OW;
+            int n, oy, ox;
+            conv_row(p, ok ? m : 0, n, oy, ox);
             if (ok) a_base[j] = n * p.IH * p.IW;
             a_y[j] = oy * p.stride - p.pad;
             a_x[j] = ox * p.stride - p.pad;
             a_ptr[j] = p.A + chunk * 8;               // + row*lda + ci0 per tile
         } else {
             if (ok) a_ptr[j] = p.A + (size_t)m * p.lda + chunk * 8;
-            a_y[j] = ((ok ? m : 0) / p.HW) % p.T;
+            a_y[j] = tconv_frame(p, ok ? m : 0);
         }
     }
     const bf16_t* b_ptr[B_IT];
@@ -133,10 +120,7 @@ __global__ __launch_bounds__(GNT) void gemm_conv_glds_kernel(const DcGemmParams 
     for (int j = 0; j < B_IT; ++j) {
         const int r = (j * 8 + wave) * 8 + srow;      // row inside the B tile
         const int chunk = pchunk ^ ((r >> 1) & 7);
-        int wrow;
-        if (GEGLU) wrow = (r < BN / 2) ? (n0 + r) : ((p.N >> 1) + n0 + (r - BN / 2));
-        else wrow = n0 + r;
-        b_ptr[j] = p.W + (size_t)wrow * p.K + chunk * 8;
+        b_ptr[j] = p.W + (size_t)gemm_wrow<BN, GEGLU>(p, n0, r) * p.K + chunk * 8;
     }
 
     // this workgroup's K tiles: all of them, or the blockIdx.y-th of sp.splits near-equal ranges
@@ -159,26 +143,22 @@ __global__ __launch_bounds__(GNT) void gemm_conv_glds_kernel(const DcGemmParams 
             if (MODE == 0) {
                 src = (a_base[j] >= 0) ? a_ptr[j] + k0 : zero_ptr;
             } else if (MODE == 1) {
-                // K is ordered (64-channel slice, tap, channel): the 9 taps of one slice are consecutive K tiles, so
-                // taps 2..9 re-read (shifted) rows that the first tap just pulled into L2
-                const int cs = kt / 9;
-                const int tap = kt - cs * 9;
-                const int dy = tap / 3, dx = tap - dy * 3;
+                int cs, tap, dy, dx;
+                conv_ktile(kt, cs, tap, dy, dx);
                 const long long toff = (long long)(dy * p.IW + dx) * p.lda + cs * 64;      // wave-uniform
                 src = ((a_base[j] >> tap) & 1) ? a_ptr[j] + toff : zero_ptr;
             } else if (MODE == 3) {
-                const int cs = kt / 9;
-                const int tap = kt - cs * 9;
+                int cs, tap, dy, dx;
+                conv_ktile(kt, cs, tap, dy, dx);
                 const int ci0 = cs * 64;
-                const int dy = tap / 3, dx = tap - dy * 3;
                 const int eh = p.IH << p.ups, ew = p.IW << p.ups;
                 const int iy = a_y[j] + dy, ix = a_x[j] + dx;
                 const bool ok = (a_base[j] >= 0) & (iy >= 0) & (iy < eh) & (ix >= 0) & (ix < ew);
                 const int srcrow = a_base[j] + (iy >> p.ups) * p.IW + (ix >> p.ups);
                 src = ok ? a_ptr[j] + (size_t)srcrow * p.lda + ci0 : zero_ptr;
             } else {
-                const int cs = kt / 3;
-                const int tap = kt - cs * 3;
+                int cs, tap;
+                tconv_ktile(kt, cs, tap);
                 const int ci0 = cs * 64;
                 const long long shift = (long long)(tap - 1) * p.HW * p.lda + ci0;
                 const int tt = a_y[j] + tap - 1;
@@ -326,47 +306,20 @@ __global__ __launch_bounds__(GNT) void gemm_conv_glds_kernel(const DcGemmParams 
             }
             if (m >= p.M || n >= n_out) continue;
             float4 v = *reinterpret_cast<const float4*>(cs + r * CS_LD + c * 4);
-            if (p.bias) {
-                const float4 bv = *reinterpret_cast<const float4*>(p.bias + n);
-                v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
-            }
+            if (p.bias) ep_add4(v, p.bias + n);
             if constexpr (GEGLU) {
                 float4 g = *reinterpret_cast<const float4*>(cs + PLANE + r * CS_LD + c * 4);
-                if (p.bias) {
-                    const float4 bg = *reinterpret_cast<const float4*>(p.bias + (p.N >> 1) + n);
-                    g.x += bg.x; g.y += bg.y; g.z += bg.z; g.w += bg.w;
-                }
-                v.x *= DC_GELU(g.x); v.y *= DC_GELU(g.y); v.z *= DC_GELU(g.z); v.w *= DC_GELU(g.w);
+                if (p.bias) ep_add4(g, p.bias + (p.N >> 1) + n);
+                ep_geglu4(v, g);
             }
-            if (p.flags & DC_GEMM_GELU) { v.x = DC_GELU(v.x); v.y = DC_GELU(v.y); v.z = DC_GELU(v.z); v.w = DC_GELU(v.w); }
-            if (p.rowvec) {
-                const float4 rv = *reinterpret_cast<const float4*>(p.rowvec + (size_t)(m / p.rows_per_vec) * p.rowvec_ld + n);
-                v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;
-            }
-            if (p.alpha != 1.0f) { v.x *= p.alpha; v.y *= p.alpha; v.z *= p.alpha; v.w *= p.alpha; }
-            if (out_f32) {
-                *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.C) + (size_t)m * p.ldc + n) = v;
-            } else {
-                uint2 pk;
-                pk.x = pack_bf2(v.x, v.y);
-                pk.y = pack_bf2(v.z, v.w);
-                if (p.residual) {
-                    const uint2 rr = *reinterpret_cast<const uint2*>(p.residual + (size_t)m * p.ldr + n);
-                    const float a0 = __uint_as_float(pk.x << 16) + __uint_as_float(rr.x << 16);
-                    const float a1 = __uint_as_float(pk.x & 0xffff0000u) + __uint_as_float(rr.x & 0xffff0000u);
-                    const float a2 = __uint_as_float(pk.y << 16) + __uint_as_float(rr.y << 16);
-                    const float a3 = __uint_as_float(pk.y & 0xffff0000u) + __uint_as_float(rr.y & 0xffff0000u);
-                    pk.x = pack_bf2(a0, a1);
-                    pk.y = pack_bf2(a2, a3);
-                }
-                *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(p.C) + (size_t)m * p.ldc + n) = pk;
-            }
+            ep_tail4(v, p, m, n);
+            ep_store4(p, out_f32, m, n, v);
         }
     }
 }
 
-// Sum of the split-K partials of the tiles [tile_begin, tile_begin + tile_count) in split order, then the same
-// epilogue as above (bias, GELU, per-row-group vector, alpha, bf16 rounding, residual). One thread per 4 channels.
+// Sum of the split-K partials of the tiles [tile_begin, tile_begin + tile_count) in split order, then the epilogue
+// (gemm_parts.h). One thread per 4 channels.
 template <int BN>
 __global__ __launch_bounds__(256) void splitk_reduce_kernel(const DcGemmParams p, const GemmSplit sp) {
     constexpr int UPR = BN / 4;
@@ -379,35 +332,11 @@ __global__ __launch_bounds__(256) void splitk_reduce_kernel(const DcGemmParams p
     const int m = (tile / tiles_n) * GBM + r, n = (tile % tiles_n) * BN + c;
     if (m >= p.M || n >= p.N) return;
     float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
-    for (int s = 0; s < sp.splits; ++s) {
-        const float4 a = *reinterpret_cast<const float4*>(sp.partial + (((size_t)s * sp.tile_count + t_loc) * GBM + r) * BN + c);
-        v.x += a.x; v.y += a.y; v.z += a.z; v.w += a.w;
-    }
-    if (p.bias) {
-        const float4 bv = *reinterpret_cast<const float4*>(p.bias + n);
-        v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
-    }
-    if (p.flags & DC_GEMM_GELU) { v.x = DC_GELU(v.x); v.y = DC_GELU(v.y); v.z = DC_GELU(v.z); v.w = DC_GELU(v.w); }
-    if (p.rowvec) {
-        const float4 rv = *reinterpret_cast<const float4*>(p.rowvec + (size_t)(m / p.rows_per_vec) * p.rowvec_ld + n);
-        v.x += rv.x; v.y += rv.y; v.z += rv.z; v.w += rv.w;
-    }
-    if (p.alpha != 1.0f) { v.x *= p.alpha; v.y *= p.alpha; v.z *= p.alpha; v.w *= p.alpha; }
-    if (p.flags & DC_GEMM_OUT_F32) {
-        *reinterpret_cast<float4*>(reinterpret_cast<float*>(p.C) + (size_t)m * p.ldc + n) = v;
-        return;
-    }
-    uint2 pk;
-    pk.x = pack_bf2(v.x, v.y);
-    pk.y = pack_bf2(v.z, v.w);
-    if (p.residual) {
-        const uint2 rr = *reinterpret_cast<const uint2*>(p.residual + (size_t)m * p.ldr + n);
-        pk.x = pack_bf2(__uint_as_float(pk.x << 16) + __uint_as_float(rr.x << 16),
-                        __uint_as_float(pk.x & 0xffff0000u) + __uint_as_float(rr.x & 0xffff0000u));
-        pk.y = pack_bf2(__uint_as_float(pk.y << 16) + __uint_as_float(rr.y << 16),
-                        __uint_as_float(pk.y & 0xffff0000u) + __uint_as_float(rr.y & 0xffff0000u));
-    }
-    *reinterpret_cast<uint2*>(reinterpret_cast<bf16_t*>(p.C) + (size_t)m * p.ldc + n) = pk;
+    for (int s = 0; s < sp.splits; ++s)
+        ep_add4(v, sp.partial + (((size_t)s * sp.tile_count + t_loc) * GBM + r) * BN + c);
+    if (p.bias) ep_add4(v, p.bias + n);
+    ep_tail4(v, p, m, n);
+    ep_store4(p, (p.flags & DC_GEMM_OUT_F32) != 0, m, n, v);
 }
 
 // ---------------------------------------------------------------------------------------------------------
@@ -447,29 +376,18 @@ __device__ __forceinline__ void persist_epilogue(f32x16_t (&acc)[2][BN / 64], co
     // bias / GEGLU / GELU / per-row-group vector / alpha, in the accumulator layout
     auto finish = [&](int mb, int nb, int q) __attribute__((always_inline)) -> float4 {
         const int m = m0 + wm * 64 + mb * 32 + fr_e;
-        const float* rv = p.rowvec ? p.rowvec + (size_t)((m < p.M ? m : 0) / p.rows_per_vec) * p.rowvec_ld : nullptr;
+        const float* rv = p.rowvec ? ep_rowvec_row(p, m < p.M ? m : 0) : nullptr;
         const int n = n0 + wn * WCOLS + nb * 32 + 8 * q + 4 * fh_e;
         const bool nok = n < n_out;
         float4 v = make_float4(acc[mb][nb][4 * q], acc[mb][nb][4 * q + 1], acc[mb][nb][4 * q + 2], acc[mb][nb][4 * q + 3]);
-        if (p.bias && nok) {
-            const float4 bv = *reinterpret_cast<const float4*>(p.bias + n);
-            v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
-        }
+        if (p.bias && nok) ep_add4(v, p.bias + n);
         if constexpr (GEGLU) {
             float4 gt = make_float4(acc[mb][nb + NBX][4 * q], acc[mb][nb + NBX][4 * q + 1],
                                     acc[mb][nb + NBX][4 * q + 2], acc[mb][nb + NBX][4 * q + 3]);
-            if (p.bias && nok) {
-                const float4 bg = *reinterpret_cast<const float4*>(p.bias + (p.N >> 1) + n);
-                gt.x += bg.x; gt.y += bg.y; gt.z += bg.z; gt.w += bg.w;
-            }
-            v.x *= DC_GELU(gt.x); v.y *= DC_GELU(gt.y); v.z *= DC_GELU(gt.z); v.w *= DC_GELU(gt.w);
+            if (p.bias && nok) ep_add4(gt, p.bias + (p.N >> 1) + n);
+            ep_geglu4(v, gt);
         }
-        if (p.flags & DC_GEMM_GELU) { v.x = DC_GELU(v.x); v.y = DC_GELU(v.y); v.z = DC_GELU(v.z); v.w = DC_GELU(v.w); }
-        if (rv && nok) {
-            const float4 r4 = *reinterpret_cast<const float4*>(rv + n);
-            v.x += r4.x; v.y += r4.y; v.z += r4.z; v.w += r4.w;
-        }
-        if (p.alpha != 1.0f) { v.x *= p.alpha; v.y *= p.alpha; v.z *= p.alpha; v.w *= p.alpha; }
+        ep_tail4(v, p, rv && nok, rv, n);
         return v;
     };
     if constexpr (EPI == 2) {
@@ -517,23 +435,14 @@ __device__ __forceinline__ void persist_epilogue(f32x16_t (&acc)[2][BN / 64], co
                 }
 #pragma unroll
                 for (int q = 0; q < 4; ++q) {   // row fr, 8-byte slot 2q+fh, XOR-swizzled by an even number per row pair
-                    const float4 v = finish(mb, nb, q);
-                    uint2 pk;
-                    pk.x = pack_bf2(v.x, v.y);
-                    pk.y = pack_bf2(v.z, v.w);
-                    *reinterpret_cast<uint2*>(ebuf + fr_e * 64 + (((2 * q + fh_e) ^ (((fr_e >> 1) & 3) << 1)) << 3)) = pk;
+                    *reinterpret_cast<uint2*>(ebuf + fr_e * 64 + (((2 * q + fh_e) ^ (((fr_e >> 1) & 3) << 1)) << 3)) = ep_pack4(finish(mb, nb, q));
                 }
 #pragma unroll
                 for (int t = 0; t < 2; ++t) {
                     const int r = t * 16 + rrow;
                     u32x4_t d = *reinterpret_cast<const u32x4_t*>(ebuf + r * 64 + ((rc ^ ((r >> 1) & 3)) << 4));
                     if (!rok[t] || ncol + nb * 32 + 8 > n_out) continue;
-                    if constexpr (EPI == 1) {
-#pragma unroll
-                        for (int e = 0; e < 4; ++e)
-                            d[e] = pack_bf2(__uint_as_float(d[e] << 16) + __uint_as_float(rr[t][e] << 16),
-                                            __uint_as_float(d[e] & 0xffff0000u) + __uint_as_float(rr[t][e] & 0xffff0000u));
-                    }
+                    if constexpr (EPI == 1) d = add_bf8(d, rr[t]);
                     *reinterpret_cast<u32x4_t*>(cbase + co[t] + nb * 64) = d;
                 }
                 __builtin_amdgcn_sched_barrier(0);
@@ -638,14 +547,10 @@ __global__ __launch_bounds__(GNT) void gemm_persist_kernel(const DcGemmParams p,
             if (MODE == 0) {
                 a_ptr[q] = ok ? p.A + (size_t)m * p.lda + chunk * 8 : nullptr;
             } else if (MODE == 1) {
-                const int ohw = p.OH * p.OW;
-                const int mm = ok ? m : 0;
-                const int n = mm / ohw;
-                const int rem = mm - n * ohw;
-                const int oy = rem / p.OW;
-                const int ox = rem - oy * p.OW;
+                int n, oy, ox;
+                conv_row(p, ok ? m : 0, n, oy, ox);
                 const int iy0 = oy * p.stride - p.pad, ix0 = ox * p.stride - p.pad;
-                int mask = 0;
+                int mask = 0;                     // conv_tap_mask, spelled here: gemm_parts.h says why
 #pragma unroll
                 for (int t = 0; t < 9; ++t) {
                     const int iy = iy0 + t / 3, ix = ix0 + t % 3;
@@ -655,17 +560,14 @@ __global__ __launch_bounds__(GNT) void gemm_persist_kernel(const DcGemmParams p,
                 a_ptr[q] = p.A + ((long long)n * p.IH * p.IW + (long long)iy0 * p.IW + ix0) * p.lda + chunk * 8;
             } else {
                 a_ptr[q] = p.A + (size_t)(ok ? m : 0) * p.lda + chunk * 8;
-                a_aux[q] = ok ? (m / p.HW) % p.T : -1000;
+                a_aux[q] = ok ? tconv_frame(p, m) : -1000;
             }
         }
 #pragma unroll
         for (int q = 0; q < B_IT; ++q) {
             const int r = (q * 8 + wave) * 8 + srow;
             const int chunk = pchunk ^ ((r >> 1) & 7);
-            int wrow;
-            if (GEGLU) wrow = (r < BN / 2) ? (n0 + r) : ((p.N >> 1) + n0 + (r - BN / 2));
-            else wrow = n0 + r;
-            b_ptr[q] = p.W + (size_t)wrow * p.K + chunk * 8;
+            b_ptr[q] = p.W + (size_t)gemm_wrow<BN, GEGLU>(p, n0, r) * p.K + chunk * 8;
         }
     };
     // quarter `part` of the next K tile's LDS-DMA (see issue_part above); part 3 advances the issue cursor
@@ -689,14 +591,13 @@ __global__ __launch_bounds__(GNT) void gemm_persist_kernel(const DcGemmParams p,
             } else if (MODE == 0) {
                 src = a_ptr[q] ? a_ptr[q] + k0 : zero_ptr;
             } else if (MODE == 1) {
-                const int cs = i_kt / 9;
-                const int tap = i_kt - cs * 9;
-                const int dy = tap / 3, dx = tap - dy * 3;
+                int cs, tap, dy, dx;
+                conv_ktile(i_kt, cs, tap, dy, dx);
                 const long long toff = (long long)(dy * p.IW + dx) * p.lda + cs * 64;      // wave-uniform
                 src = ((a_aux[q] >> tap) & 1) ? a_ptr[q] + toff : zero_ptr;
             } else {
-                const int cs = i_kt / 3;
-                const int tap = i_kt - cs * 3;
+                int cs, tap;
+                tconv_ktile(i_kt, cs, tap);
                 const long long shift = (long long)(tap - 1) * p.HW * p.lda + cs * 64;
                 const int tt = a_aux[q] + tap - 1;
                 src = (tt >= 0 && tt < p.T) ? a_ptr[q] + shift : zero_ptr;

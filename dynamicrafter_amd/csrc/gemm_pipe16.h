@@ -87,39 +87,21 @@ void gemm_pipe320x16_kernel(const DcGemmParams p, const GemmSplit sp) {
             rowoff[rb] = (unsigned)mm * lda2 + lq_a * 16;
             mask[rb] = ok ? 1 : 0;
         } else if (MODE == 1) {
-            const int ohw = p.OH * p.OW;
-            const int n = mm / ohw;
-            const int rem = mm - n * ohw;
-            const int oy = rem / p.OW;
-            const int ox = rem - oy * p.OW;
+            int n, oy, ox;
+            conv_row(p, mm, n, oy, ox);
             const int iy0 = oy * p.stride - p.pad, ix0 = ox * p.stride - p.pad;
-            int mk = 0;
-#pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                const int iy = iy0 + t / 3, ix = ix0 + t % 3;
-                if (ok && iy >= 0 && iy < p.IH && ix >= 0 && ix < p.IW) mk |= 1 << t;
-            }
-            mask[rb] = mk;
+            mask[rb] = conv_tap_mask(ok, iy0, ix0, p.IH, p.IW);
             rowoff[rb] = (unsigned)(((n * p.IH + iy0 + p.pad) * p.IW + ix0 + p.pad)) * lda2 + lq_a * 16;
         } else if (MODE == 3) {
             // nearest x2 upsampling fused into the conv (stride 1, pad 1): tap (dy, dx) of output pixel (oy, ox) reads input pixel
             // ((oy + dy - 1) >> 1, (ox + dx - 1) >> 1) = centre (oy >> 1, ox >> 1) + (ry, rx), ry = {py - 1, 0, py}[dy] with py = oy & 1
             // (rx likewise): the offset is the centre's (+ bias) and two per-lane selects by the parities (mask bits 9, 10)
-            const int ohw = p.OH * p.OW;
-            const int n = mm / ohw;
-            const int rem = mm - n * ohw;
-            const int oy = rem / p.OW;
-            const int ox = rem - oy * p.OW;
-            int mk = 0;
-#pragma unroll
-            for (int t = 0; t < 9; ++t) {
-                const int uy = oy + t / 3 - 1, ux = ox + t % 3 - 1;
-                if (ok && uy >= 0 && uy < p.OH && ux >= 0 && ux < p.OW) mk |= 1 << t;
-            }
-            mask[rb] = mk | ((oy & 1) << 9) | ((ox & 1) << 10);
+            int n, oy, ox;
+            conv_row(p, mm, n, oy, ox);
+            mask[rb] = conv_tap_mask(ok, oy - 1, ox - 1, p.OH, p.OW) | ((oy & 1) << 9) | ((ox & 1) << 10);
             rowoff[rb] = (unsigned)(((n * p.IH + (oy >> 1) + 1) * p.IW + (ox >> 1) + 1)) * lda2 + lq_a * 16;
         } else {
-            const int frame = (mm / p.HW) % p.T;
+            const int frame = (mm / p.HW) % p.T;   // tconv_frame; spelled here with the mask: gemm_parts.h says why
             int mk = 0;
 #pragma unroll
             for (int t = 0; t < 3; ++t) {
@@ -139,18 +121,14 @@ void gemm_pipe320x16_kernel(const DcGemmParams p, const GemmSplit sp) {
         ars[3] = 0x00020000;
     }
     auto a_tile = [&](int kt, unsigned (&vo)[4], int& soff) __attribute__((always_inline)) {
-        int tap = 0;
+        int cs, tap = 0, dy, dx;
         if (MODE == 0) {
             soff = kt * 128;
         } else if (MODE == 1) {
-            const int cs = kt / 9;
-            tap = kt - cs * 9;
-            const int dy = tap / 3, dx = tap - dy * 3;
+            conv_ktile(kt, cs, tap, dy, dx);
             soff = (dy * p.IW + dx) * (int)lda2 + cs * 128;
         } else if (MODE == 3) {
-            const int cs = kt / 9;
-            tap = kt - cs * 9;
-            const int dy = tap / 3, dx = tap - dy * 3;
+            conv_ktile(kt, cs, tap, dy, dx);
             soff = cs * 128;
             const int y0 = dy == 0 ? -p.IW * (int)lda2 : 0, y1 = dy == 2 ? p.IW * (int)lda2 : 0;      // by the row parity
             const int x0 = dx == 0 ? -(int)lda2 : 0, x1 = dx == 2 ? (int)lda2 : 0;                    // by the column parity
@@ -161,8 +139,7 @@ void gemm_pipe320x16_kernel(const DcGemmParams p, const GemmSplit sp) {
             }
             return;
         } else {
-            const int cs = kt / 3;
-            tap = kt - cs * 3;
+            tconv_ktile(kt, cs, tap);
             soff = tap * p.HW * (int)lda2 + cs * 128;
         }
 #pragma unroll
@@ -347,7 +324,7 @@ void gemm_pipe320x16_kernel(const DcGemmParams p, const GemmSplit sp) {
 #pragma unroll
     for (int rb = 0; rb < 4; ++rb) {
         const int m_acc = m0 + wave * 64 + rb * 16 + er;
-        const float* rv = p.rowvec ? p.rowvec + (size_t)((m_acc < p.M ? m_acc : 0) / p.rows_per_vec) * p.rowvec_ld : nullptr;
+        const float* rv = p.rowvec ? ep_rowvec_row(p, m_acc < p.M ? m_acc : 0) : nullptr;
         int mr = m0 + wave * 64 + rb * 16 + rrow;
         const bool rok = mr < p.M;
         if (!rok) mr = p.M - 1;                             // clamped rows are loaded, never stored
@@ -362,30 +339,14 @@ void gemm_pipe320x16_kernel(const DcGemmParams p, const GemmSplit sp) {
                 const int cb = 2 * cp + h;
                 const int n = n0 + cb * 16 + 4 * eq;
                 float4 v = make_float4(acc[rb][cb][0], acc[rb][cb][1], acc[rb][cb][2], acc[rb][cb][3]);
-                if (p.bias) {
-                    const float4 bv = *reinterpret_cast<const float4*>(p.bias + n);
-                    v.x += bv.x; v.y += bv.y; v.z += bv.z; v.w += bv.w;
-                }
-                if (p.flags & DC_GEMM_GELU) { v.x = DC_GELU(v.x); v.y = DC_GELU(v.y); v.z = DC_GELU(v.z); v.w = DC_GELU(v.w); }
-                if (rv) {
-                    const float4 r4 = *reinterpret_cast<const float4*>(rv + n);
-                    v.x += r4.x; v.y += r4.y; v.z += r4.z; v.w += r4.w;
-                }
-                if (p.alpha != 1.0f) { v.x *= p.alpha; v.y *= p.alpha; v.z *= p.alpha; v.w *= p.alpha; }
-                uint2 pk;
-                pk.x = pack_bf2(v.x, v.y);
-                pk.y = pack_bf2(v.z, v.w);
+                if (p.bias) ep_add4(v, p.bias + n);
+                ep_tail4(v, p, rv != nullptr, rv, n);
                 // patch: row er (64 bytes), 8-byte slot 4 h + eq, XOR-swizzled by the row pair so that the 16-byte read-back below
                 // and these 8-byte stores both spread over the banks
-                *reinterpret_cast<uint2*>(ebuf + er * 64 + ((((4 * h + eq) ^ (((er >> 1) & 3) << 1))) << 3)) = pk;
+                *reinterpret_cast<uint2*>(ebuf + er * 64 + ((((4 * h + eq) ^ (((er >> 1) & 3) << 1))) << 3)) = ep_pack4(v);
             }
             u32x4_t d = *reinterpret_cast<const u32x4_t*>(ebuf + rrow * 64 + ((rc ^ ((rrow >> 1) & 3)) << 4));
-            if constexpr (EPI == 1) {
-#pragma unroll
-                for (int e = 0; e < 4; ++e)
-                    d[e] = pack_bf2(__uint_as_float(d[e] << 16) + __uint_as_float(rr[e] << 16),
-                                    __uint_as_float(d[e] & 0xffff0000u) + __uint_as_float(rr[e] & 0xffff0000u));
-            }
+            if constexpr (EPI == 1) d = add_bf8(d, rr);
             if (rok) *reinterpret_cast<u32x4_t*>(cbase + co + cp * 64) = d;
             __builtin_amdgcn_sched_barrier(0);
         }

@@ -268,12 +268,8 @@ void gemm_pp_kernel(const DcGemmParams p, const GemmSplit sp, const int tile_gro
 #pragma unroll
         for (int c = 0; c < 4; ++c) {
             float4 v = make_float4(acc[rb][c][0] + bv[c].x, acc[rb][c][1] + bv[c].y, acc[rb][c][2] + bv[c].z, acc[rb][c][3] + bv[c].w);
-            v.x *= DC_GELU(acc[rb][c + 4][0] + bg[c].x); v.y *= DC_GELU(acc[rb][c + 4][1] + bg[c].y);
-            v.z *= DC_GELU(acc[rb][c + 4][2] + bg[c].z); v.w *= DC_GELU(acc[rb][c + 4][3] + bg[c].w);
-            uint2 pk;
-            pk.x = pack_bf2(v.x, v.y);
-            pk.y = pack_bf2(v.z, v.w);
-            *reinterpret_cast<uint2*>(ebuf + er * 128 + (((4 * c + eq) ^ (((er >> 1) & 7) << 1)) << 3)) = pk;
+            ep_geglu4(v, make_float4(acc[rb][c + 4][0] + bg[c].x, acc[rb][c + 4][1] + bg[c].y, acc[rb][c + 4][2] + bg[c].z, acc[rb][c + 4][3] + bg[c].w));
+            *reinterpret_cast<uint2*>(ebuf + er * 128 + (((4 * c + eq) ^ (((er >> 1) & 7) << 1)) << 3)) = ep_pack4(v);
         }
 #pragma unroll
         for (int h = 0; h < 2; ++h) {

@@ -112,6 +112,26 @@ def test_lds_dma_asm_lives_in_lds_stage_h_only():
     assert users == ["lds_stage.h"], users
 
 
+def test_gemm_parts_are_spelled_once():
+    """One spelling of the packed bf16 residual add (csrc/dc_common.h: add_bf2 / add_bf8) and of the conv modes' tap-validity
+    masks (csrc/gemm_parts.h): no kernel file writes either out by hand. Two named exemptions, each one loop, because every
+    other spelling changed instructions inside the kernel's K loop (profiles/gemm_parts_isa.txt): set_issue_tile of
+    gemm_persist_kernel (gemm_conv_glds.hip) and the 3-bit temporal mask of gemm_pipe320x16_kernel (gemm_pipe16.h)."""
+    def code(path):
+        text = open(path).read()
+        return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+    files = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".h")))
+    assert "gemm_parts.h" in files and "dc_common.h" in files and len(files) > 10
+    adders = [f for f in files if "& 0xffff0000u) + __uint_as_float(" in code(os.path.join(CSRC, f))]
+    assert adders == ["dc_common.h"], adders
+    maskers = {f: code(os.path.join(CSRC, f)).count("|= 1 << t") for f in files}
+    assert {f: n for f, n in maskers.items() if n} == {"gemm_parts.h": 1, "gemm_conv_glds.hip": 1, "gemm_pipe16.h": 1}, maskers
+    glds = code(os.path.join(CSRC, "gemm_conv_glds.hip"))
+    assert glds.index("auto set_issue_tile") < glds.index("|= 1 << t") < glds.index("auto issue_next_part")
+    pipe = code(os.path.join(CSRC, "gemm_pipe16.h"))
+    assert "tt < p.T) mk |= 1 << t" in pipe
+
+
 def _tiny_model(config_name, extra=None):
     from dynamicrafter_amd.utils.utils import instantiate_from_config
     from tests.golden_cfg import TINY_AE, TINY_UNET

@@ -7,10 +7,16 @@ For every kernel: `identical` when the normalised text of its body is the same o
 "skeleton" - the MFMA, ds_read* / ds_write*, global_load* / global_store* (LDS-DMA included), s_barrier and s_waitcnt
 instructions, the last with their counter operands - is the same, with the instruction-count delta (where it is not: whether
 the lines that differ are all `s_waitcnt lgkmcnt`, i.e. waits moved or merged, or the order of other instructions, and how
-many skeleton lines are involved; `, registers` where next_free_vgpr, accum_offset or the LDS size differ or the private
-segment grew); then the instruction count of the second file, the registers, the LDS size and the private segment from the kernel descriptor (.amdhsa_*), `parent -> this` where they differ.
+many skeleton lines are involved; `, registers` where next_free_vgpr or accum_offset differ - `, fewer registers` where neither
+grew: recorded, inside the gate -, the LDS size differs or the private segment grew);
+for every kernel that is not identical `+N -M in MFMA span`: the instructions of the second file between its first and last
+v_mfma that a diff of the two bodies (register numbers and labels blanked) does not match to the first file, and the first
+file's instructions those diff blocks leave out, nothing netted (+0 -0 = every change lies in the prologue or the epilogue); then the instruction count of
+the second file, the registers, the LDS size and the private segment from the kernel descriptor (.amdhsa_*), `parent -> this`
+where they differ.
 Normalisation: __hip_cuid_<hash> (derived from the source text) and comments. Exit status 1 if a kernel is neither
-identical nor skeleton-identical with equal next_free_vgpr / accum_offset / LDS and a private segment that did not grow.
+identical nor skeleton-identical, changes inside its MFMA span, next_free_vgpr / accum_offset or the private segment grew, or the
+LDS size differs.
 """
 import difflib
 import re
@@ -74,6 +80,27 @@ def instructions(body):
     return [l for l in body if not l.endswith(":")]
 
 
+def changed_in_mfma_span(body_a, body_b):
+    """-> (added, dropped): the instructions of body_b between its first and last v_mfma that a diff of the two bodies (register
+    numbers and labels blanked) does not match to body_a, and the instructions of body_a that the same diff blocks leave out.
+    Nothing is netted: n instructions replaced by n others count +n -n."""
+    blank = lambda l: re.sub(r"\b[vsa]\d+\b|\b[vsa]\[\d+:\d+\]|\.LBB\d+_\d+", "R", l)
+    a, b = [blank(l) for l in instructions(body_a)], [blank(l) for l in instructions(body_b)]
+    mfma = [i for i, l in enumerate(b) if l.startswith("v_mfma")]
+    if not mfma:
+        return 0, 0
+    lo, hi = mfma[0], mfma[-1]
+    added = dropped = 0
+    for op, i1, i2, j1, j2 in difflib.SequenceMatcher(None, a, b, autojunk=False).get_opcodes():
+        if op == "equal":
+            continue
+        inside = sum(1 for j in range(j1, j2) if lo < j < hi)
+        added += inside
+        if inside or (j1 == j2 and lo < j1 <= hi):          # the parent's side of a block that touches the span
+            dropped += i2 - i1
+    return added, dropped
+
+
 def main():
     if len(sys.argv) != 3:
         sys.exit(__doc__)
@@ -102,10 +129,17 @@ def main():
             what = "lgkmcnt waits" if all(l.startswith("s_waitcnt lgkmcnt") for l in moved) else "order"
             code = f"skeleton differs ({what}: {len(moved)} lines), {nb - na:+d} insns"
             ok = False
-        if any(da[f] != db[f] for f in ("next_free_vgpr", "accum_offset", "group_segment_fixed_size")) or \
+        regs = ("next_free_vgpr", "accum_offset")
+        if any(db[f] > da[f] for f in regs) or da["group_segment_fixed_size"] != db["group_segment_fixed_size"] or \
                 db["private_segment_fixed_size"] > da["private_segment_fixed_size"]:
             code += ", registers"
             ok = False
+        elif any(db[f] < da[f] for f in regs):
+            code += ", fewer registers"
+        if code != "identical":
+            span = changed_in_mfma_span(ka["body"], kb["body"])
+            code += ", +%d -%d in MFMA span" % span
+            ok = ok and span == (0, 0)
         bad += not ok
         col = lambda f: str(da[f]) if da[f] == db[f] else f"{da[f]}->{db[f]}"
         print(f"{short:<58} {code:<66} {nb:>6} {col('next_free_vgpr'):>5} {col('accum_offset'):>5} {col('next_free_sgpr'):>9} "
