@@ -116,6 +116,9 @@ SIGNATURES = {
     "dc_jpeg_dct_quant": (_I, [_P, _P, _P, _I, _I, _I, _P]),
     "dc_jpeg_entropy": (_I, [_P, _P, _P, _I, _I, _I, _I, _L, _P]),
     "dc_jpeg_pack": (_I, [_P, _P, _P, _P, _P, _I, _I, _L, _L, _P]),
+    "dc_jpeg_decode_entropy": (_I, [_P, _L, _P, _P, _P, _P, _P] + [_I] * 8 + [_P]),
+    "dc_jpeg_decode_idct": (_I, [_P, _P, _P] + [_I] * 6 + [_P]),
+    "dc_jpeg_decode_output": (_I, [_P, _P] + [_I] * 7 + [_P]),
     "dc_gif_histogram": (_I, [_P, _P, _I, _I, _I, _P]),
     "dc_gif_map": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "dc_gif_lzw": (_I, [_P, _P, _P, _I, _I, _I, _L, _P]),

@@ -9,26 +9,12 @@
 // gfx950 only (wave64: one 8x8 block is one wave, a lane per coefficient).
 #include "dc_common.h"
 #include "dcrafter_hip.h"
+#include "jpeg_tables.h"
 
 namespace {
 
-// orthonormal DCT-II: D[u][x] = c(u) / 2 cos((2x + 1) u pi / 16), c(0) = 1 / sqrt 2 (fp32 roundings of the exact values)
-__device__ const float kDct[64] = {
-    0.353553385f, 0.353553385f, 0.353553385f, 0.353553385f, 0.353553385f, 0.353553385f, 0.353553385f, 0.353553385f,
-    0.490392625f, 0.415734798f, 0.277785122f, 0.0975451618f, -0.0975451618f, -0.277785122f, -0.415734798f, -0.490392625f,
-    0.461939752f, 0.191341713f, -0.191341713f, -0.461939752f, -0.461939752f, -0.191341713f, 0.191341713f, 0.461939752f,
-    0.415734798f, -0.0975451618f, -0.490392625f, -0.277785122f, 0.277785122f, 0.490392625f, 0.0975451618f, -0.415734798f,
-    0.353553385f, -0.353553385f, -0.353553385f, 0.353553385f, 0.353553385f, -0.353553385f, -0.353553385f, 0.353553385f,
-    0.277785122f, -0.490392625f, 0.0975451618f, 0.415734798f, -0.415734798f, -0.0975451618f, 0.490392625f, -0.277785122f,
-    0.191341713f, -0.461939752f, 0.461939752f, -0.191341713f, -0.191341713f, 0.461939752f, -0.461939752f, 0.191341713f,
-    0.0975451618f, -0.277785122f, 0.415734798f, -0.490392625f, 0.490392625f, -0.415734798f, 0.277785122f, -0.0975451618f,
-};
-
-// zigzag scan: kZigzag[k] = 8 * row + col of the k-th coefficient (T.81 figure 5)
-__device__ const uint8_t kZigzag[64] = {
-    0, 1, 8, 16, 9, 2, 3, 10, 17, 24, 32, 25, 18, 11, 4, 5, 12, 19, 26, 33, 40, 48, 41, 34, 27, 20, 13, 6, 7, 14, 21, 28,
-    35, 42, 49, 56, 57, 50, 43, 36, 29, 22, 15, 23, 30, 37, 44, 51, 58, 59, 52, 45, 38, 31, 39, 46, 53, 60, 61, 54, 47, 55, 62, 63,
-};
+using dc_jpeg::kDct;          // jpeg_tables.h: shared with the decoder (jpeg_decode.hip)
+using dc_jpeg::kZigzag;
 
 // ---------------------------------------------------------------------------------------------- stage 1: coefficients
 // One workgroup per MCU, one thread per pixel. All arithmetic fp32: Y/Cb/Cr per pixel, chroma = mean of its 2x2 pixels, level

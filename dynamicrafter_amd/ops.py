@@ -974,6 +974,67 @@ def jpeg_pack(scratch, seg_len, seg_off, out, frame_len, *, T, segs_per_frame, s
     return out
 
 
+# ---------------------------------------------------------------------------------------------- JPEG decoding (csrc/jpeg_decode.hip)
+JPEG_FRAME_TAB_BYTES = 1352                     # DC_JPEG_FRAME_TAB_BYTES of include/dcrafter_hip.h
+JPEG_SEG_STATUS = {1: "a code that is in no table", 2: "a zero run past coefficient 63", 3: "a DC category above 11 or an AC "
+                   "category above 10", 4: "bytes left over", 5: "bytes missing", 6: "a descriptor outside the batch"}
+
+
+def jpeg_decode_geometry(H, W, ncomp, hs, vs):
+    """(my, mx, blocks per MCU, bytes of one frame's padded sample planes) of a frame; ValueError for a sampling the decoder
+    does not take."""
+    if (ncomp, hs, vs) not in ((1, 1, 1), (3, 1, 1), (3, 2, 1), (3, 2, 2)):
+        raise ValueError(f"jpeg_decode: {ncomp} components with luma sampling {hs}x{vs} (1 or 3 components; 1x1, 2x1 or 2x2)")
+    my, mx = (H + 8 * vs - 1) // (8 * vs), (W + 8 * hs - 1) // (8 * hs)
+    bpm = hs * vs + (2 if ncomp == 3 else 0)
+    return my, mx, bpm, my * mx * 64 * bpm
+
+
+def jpeg_decode_entropy(scan, seg, frame_seg, ftab, coef, status, *, T, my, mx, ncomp, hs, vs, max_segs_per_frame):
+    """scan uint8 (the segments' bytes), seg int32 [n_seg, 5] (offset, length, first MCU, MCUs, frame), frame_seg int32 [T + 1],
+    ftab uint8 [T, JPEG_FRAME_TAB_BYTES] -> coef int16 [T, my, mx, bpm, 64] (zigzag order), status int32 [n_seg]."""
+    _flat(scan, torch.uint8, "scan"); _flat(ftab, torch.uint8, "ftab"); _flat(coef, torch.int16, "coef")
+    for t, name in ((seg, "seg"), (frame_seg, "frame_seg"), (status, "status")):
+        _flat(t, torch.int32, name)
+    bpm = jpeg_decode_geometry(8 * vs * my, 8 * hs * mx, ncomp, hs, vs)[2]
+    n_seg = seg.numel() // 5
+    if min(T, my, mx, n_seg, max_segs_per_frame, scan.numel()) < 1 or seg.numel() != 5 * n_seg:
+        raise ValueError(f"jpeg_decode_entropy: T {T}, my {my}, mx {mx}, {seg.numel()} descriptor words, {scan.numel()} bytes")
+    _need(frame_seg, T + 1, "frame_seg"); _need(ftab, T * JPEG_FRAME_TAB_BYTES, "ftab"); _need(status, n_seg, "status")
+    _need(coef, T * my * mx * bpm * 64, "coef")
+    _launch("jpeg_decode_entropy", 0.0, scan.numel() + 2.0 * T * my * mx * bpm * 64, _hip.lib().dc_jpeg_decode_entropy, _ptr(scan),
+            scan.numel(), _ptr(seg), _ptr(frame_seg), _ptr(ftab), _ptr(coef), _ptr(status), n_seg, T, my, mx, ncomp, hs, vs,
+            max_segs_per_frame, stream_ptr())
+    return coef
+
+
+def jpeg_decode_idct(coef, ftab, planes, *, T, my, mx, ncomp, hs, vs):
+    """coef int16 [T, my, mx, bpm, 64] -> planes uint8, per frame Y [my 8 vs, mx 8 hs] then Cb, Cr [my 8, mx 8]."""
+    _flat(coef, torch.int16, "coef"); _flat(ftab, torch.uint8, "ftab"); _flat(planes, torch.uint8, "planes")
+    n = jpeg_decode_geometry(8 * vs * my, 8 * hs * mx, ncomp, hs, vs)[3]
+    if min(T, my, mx) < 1:
+        raise ValueError(f"jpeg_decode_idct: T {T}, my {my}, mx {mx}")
+    _need(coef, T * n, "coef"); _need(ftab, T * JPEG_FRAME_TAB_BYTES, "ftab"); _need(planes, T * n, "planes")
+    _launch("jpeg_decode_idct", 32.0 * T * n, 3.0 * T * n, _hip.lib().dc_jpeg_decode_idct, _ptr(coef), _ptr(ftab), _ptr(planes), T,
+            my, mx, ncomp, hs, vs, stream_ptr())
+    return planes
+
+
+def jpeg_decode_output(planes, out, *, T, H, W, ncomp, hs, vs):
+    """planes -> out: uint8 [T, H, W, 3], or fp32 [T, 3, H, W] holding the same integers (chosen by out's dtype)."""
+    _flat(planes, torch.uint8, "planes")
+    if out.dtype not in (torch.uint8, torch.float32):
+        raise ValueError(f"jpeg_decode_output: out must be uint8 [T, H, W, 3] or fp32 [T, 3, H, W], got {out.dtype}")
+    _flat(out, out.dtype, "out")
+    if min(T, H, W) < 1 or max(H, W) > 65535:
+        raise ValueError(f"jpeg_decode_output: T {T}, H {H}, W {W}")
+    n = jpeg_decode_geometry(H, W, ncomp, hs, vs)[3]
+    _need(planes, T * n, "planes"); _need(out, T * H * W * 3, "out")
+    _launch("jpeg_decode_output", 0.0, T * n + T * H * W * 3.0 * out.element_size(), _hip.lib().dc_jpeg_decode_output, _ptr(planes),
+            _ptr(out), T, H, W, ncomp, hs, vs, 1 if out.dtype == torch.float32 else 0, stream_ptr())
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- animated GIF (csrc/gif.hip)
 GIF_HIST_BINS = 32768                           # DC_GIF_HIST_BINS of include/dcrafter_hip.h
 GIF_CLEAR_INTERVAL = 3838                       # DC_GIF_CLEAR_INTERVAL: data codes in front of a Clear inside a chunk

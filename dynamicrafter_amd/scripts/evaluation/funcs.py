@@ -4,8 +4,8 @@ reference's `scripts/evaluation/funcs.py`, same names and signatures.
     batch_ddim_sampling      funcs.py:14-80     conditioning dict -> unconditional branch -> DDIM loop -> decode
     get_filelist, get_dirlist   funcs.py:83-97  sorted glob by one extension / sorted sub-directories
     load_model_checkpoint, load_prompts, get_latent_z   funcs.py:100-140, 221-226   re-exported from inference.py (one copy)
-    load_image_batch         funcs.py:182-203   image files -> [n, 3, h, w] in [-1, 1] on the device
-    load_video_batch         funcs.py:143-179   raises: there is no video decoder in this package
+    load_image_batch         funcs.py:182-203   image files (or the first frame of an .avi) -> [n, 3, h, w] in [-1, 1] on the device
+    load_video_batch         funcs.py:143-179   Motion-JPEG .avi clips -> [b, 3, t, h, w] in [-1, 1] on the device (HIP JPEG decoder)
     save_videos              funcs.py:206-218   [b, n_samples, c, t, h, w] -> one clip file per batch entry
 
 `get_filelist(data_dir, ext="*")` here is the reference's funcs.py signature; inference.py keeps its own
@@ -98,32 +98,95 @@ def get_dirlist(path):
     return out
 
 
-_NO_VIDEO = ("{name}: reading a video needs a decoder (the reference uses decord), and this package ships none; decode the "
-             "frames yourself and pass images (.png / .jpg), or tensors to get_latent_z")
+_NO_VIDEO = ("{name}: the only video format this package decodes is Motion-JPEG in an AVI container (.avi; utils/load_video.py, "
+             "what save_videos(container='avi') writes); the reference reads other codecs through decord, which is not available "
+             "here. Re-encode the clip as MJPEG AVI, or pass images (.png / .jpg), or tensors to get_latent_z")
 
 
-def load_video_batch(filepath_list, frame_stride, video_size=(256, 256), video_frames=16):
-    """funcs.py:143-179 reads clips through decord. Not available here: raises NotImplementedError."""
-    raise NotImplementedError(_NO_VIDEO.format(name="load_video_batch"))
+def video_frame_indices(total_frames, frame_stride, video_frames):
+    """The frame selection of funcs.py:156-173 for a clip of `total_frames`: (indices, padding, frame_stride). max_valid =
+    (total - 1) // frame_stride + 1; video_frames < 0 asks for every frame and sets the stride to 1 (the count of frames read is
+    still capped by max_valid of the stride that was passed, as in the reference); indices = frame_stride * i; `padding` = how
+    often the last frame read is repeated to reach the required count. The returned stride is the one later files of the same
+    call see (the reference overwrites its argument). Host arithmetic only."""
+    if not frame_stride > 0:
+        raise ValueError("valid frame stride should be a positive integer!")
+    max_valid_frames = (total_frames - 1) // frame_stride + 1
+    if video_frames < 0:
+        required_frames, frame_stride = total_frames, 1
+    else:
+        required_frames = video_frames
+    query_frames = min(required_frames, max_valid_frames)
+    return [frame_stride * i for i in range(query_frames)], max(required_frames - max_valid_frames, 0), frame_stride
+
+
+def _jpeg_frames_normalised(frames, indices, size, device):
+    """Frames `indices` of a Motion-JPEG clip (its JPEG files) -> fp32 [t, 3, size[0], size[1]] in [-1, 1] on the device: decoded to fp32 planes by
+    the HIP JPEG decoder, resized with ops.resize_f32(antialias=False) only when the file's size differs, (x / 255 - 0.5) * 2."""
+    from ... import ops
+    from ...utils.load_video import decode_jpeg_frames
+    planes = decode_jpeg_frames([frames[i] for i in indices], device=device, planar=True)         # [t, 3, H, W], 0..255
+    t, _, H, W = planes.shape
+    h, w = int(size[0]), int(size[1])
+    if (H, W) != (h, w):
+        planes = ops.resize_f32(planes.view(3 * t, H, W), (h, w), antialias=False).view(t, 3, h, w)
+    return (planes / 255. - 0.5) * 2
+
+
+def _device(device, name):
+    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
+    if device.type != "cuda":
+        raise RuntimeError(f"{name} decodes and resamples on the HIP path only (there is no CPU fallback)")
+    return device
+
+
+def load_video_batch(filepath_list, frame_stride, video_size=(256, 256), video_frames=16, device=None):
+    """funcs.py:143-179: every clip -> fp32 [3, t, video_size[0], video_size[1]] in [-1, 1], stacked to [b, 3, t, h, w] on
+    `device` (default: the current HIP device; the reference returns a CPU tensor). The reference reads through decord; here a
+    clip is a Motion-JPEG `.avi` (utils/load_video.py), and only the frames `video_frame_indices` selects are decoded.
+    `video_frames=-1` takes every frame with stride 1; a clip that is too short repeats its last frame, with the reference's
+    message. decord scales to `video_size` inside its reader with its own (swscale) filter, which is not reproduced: a clip
+    whose size differs is resized to exactly `video_size` with ops.resize_f32(antialias=False), bilinear on the decoded fp32
+    values, and a clip of that size is not touched. Any other extension, `.mp4` included, raises NotImplementedError before the
+    file is opened."""
+    for filepath in filepath_list:
+        if os.path.splitext(os.path.split(filepath)[1])[1] != ".avi":
+            raise NotImplementedError(_NO_VIDEO.format(name=f"load_video_batch({filepath!r})"))
+    from ...utils.load_video import read_avi_mjpeg
+    device = _device(device, "load_video_batch")
+    batch_tensor = []
+    for filepath in filepath_list:
+        frames = read_avi_mjpeg(filepath)[3]
+        indices, padding_num, frame_stride = video_frame_indices(len(frames), frame_stride, video_frames)
+        frame_tensor = _jpeg_frames_normalised(frames, indices, video_size, device).permute(1, 0, 2, 3)       # [c, t, h, w]
+        if padding_num:
+            frame_tensor = torch.cat([frame_tensor, *([frame_tensor[:, -1:, :, :]] * padding_num)], dim=1)
+            print(f'{os.path.split(filepath)[1]} is not long enough: {padding_num} frames padded.')
+        batch_tensor.append(frame_tensor.contiguous())
+    return torch.stack(batch_tensor, dim=0)
 
 
 def load_image_batch(filepath_list, image_size=(256, 256), device=None):
     """funcs.py:182-203: every file -> fp32 [3, image_size[0], image_size[1]] in [-1, 1], stacked to [n, 3, h, w]. `.png` and
     `.jpg` are decoded with Pillow to float32 and resized to exactly `image_size` (aspect is not kept) on the device with
     ops.resize_f32(antialias=False), the equivalent of the reference's cv2.resize(INTER_LINEAR) on float32; then (x / 255 - 0.5)
-    * 2. The result stays on `device` (default: the current HIP device), where the reference returns a CPU tensor. `.mp4`
-    raises NotImplementedError (no video decoder); other extensions raise it as in the reference."""
+    * 2. The result stays on `device` (default: the current HIP device), where the reference returns a CPU tensor. `.avi`
+    (Motion-JPEG) gives the clip's first frame through the HIP JPEG decoder, resized the same way, as the reference's `.mp4`
+    branch does through decord. `.mp4` raises NotImplementedError (no decoder for its codecs); other extensions raise it as in
+    the reference."""
     from PIL import Image
     from ... import ops
-    device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    if device.type != "cuda":
-        raise RuntimeError("load_image_batch resamples on the HIP path only (there is no CPU fallback)")
+    from ...utils.load_video import read_avi_mjpeg
+    device = _device(device, "load_image_batch")
     h, w = int(image_size[0]), int(image_size[1])
     batch_tensor = []
     for filepath in filepath_list:
         _, ext = os.path.splitext(os.path.split(filepath)[1])
         if ext == ".mp4":
             raise NotImplementedError(_NO_VIDEO.format(name=f"load_image_batch({filepath!r})"))
+        if ext == ".avi":
+            batch_tensor.append(_jpeg_frames_normalised(read_avi_mjpeg(filepath)[3], [0], (h, w), device)[0])
+            continue
         if ext not in (".png", ".jpg"):
             raise NotImplementedError(f"ERROR: <{ext}> image loading only support format: [png], [jpg]")
         rgb = np.array(Image.open(filepath).convert("RGB"), np.float32)                       # [H, W, 3], 0..255

@@ -457,6 +457,54 @@ int dc_jpeg_entropy(const int16_t* coef, uint8_t* scratch, int32_t* seg_len, int
 int dc_jpeg_pack(const uint8_t* scratch, const int32_t* seg_len, int32_t* seg_off, uint8_t* out, int32_t* frame_len, int T,
                  int segs_per_frame, int64_t stride, int64_t frame_stride, void* stream);
 
+/* ---- baseline JPEG decoding (T.81 SOF0, 8-bit, one interleaved scan) for Motion-JPEG input ----
+ * Together the three entries stand where the reference reads a clip through decord (VideoReader.get_batch:
+ * scripts/evaluation/funcs.py:154-169, and the first frame of a clip at :188-190); the host walks the AVI container and the JFIF
+ * headers and cuts the scans into segments (dynamicrafter_amd/utils/load_video.py). A batch is T frames of one geometry:
+ * ncomp = 1 (grey; hs = vs = 1) or 3 (YCbCr, luma sampling hs x vs = 1x1, 2x1 or 2x2, chroma 1x1). An MCU is 8 hs x 8 vs
+ * pixels and holds hs vs luma blocks (row-major) followed by Cb and Cr: bpm = hs vs + 2 blocks (1 for grey);
+ * my = ceil(H / (8 vs)), mx = ceil(W / (8 hs)). Tables may differ from frame to frame. */
+
+/* Per frame one table block of DC_JPEG_FRAME_TAB_BYTES bytes: the Huffman tables DC0, DC1, AC0, AC1 (each BITS[16] then
+ * HUFFVAL[256], unused tail zero; a table the frame lacks is all zero), 4 quantisation tables of 64 bytes in zigzag order,
+ * 3 bytes Td | Ta << 4 (one per component), 3 bytes Tq (one per component), 2 bytes padding. */
+#define DC_JPEG_FRAME_TAB_BYTES 1352
+
+/* status word of a segment after dc_jpeg_decode_entropy: 0 = decoded, else why its lane stopped */
+#define DC_JPEG_ST_CODE 1         /* the next bits start no code of the table (or a symbol baseline scans do not have) */
+#define DC_JPEG_ST_RUN 2          /* a zero run passes coefficient 63 */
+#define DC_JPEG_ST_CATEGORY 3     /* a DC category above 11 or an AC category above 10 */
+#define DC_JPEG_ST_LEFTOVER 4     /* all MCUs decoded, a whole byte or more of the segment is left (or it holds a marker) */
+#define DC_JPEG_ST_MISSING 5      /* the MCUs need more bits than the segment holds */
+#define DC_JPEG_ST_DESCRIPTOR 6   /* the segment's descriptor points outside the scan buffer, the frame's MCUs or its frame */
+
+/* Entropy decoding. scan[scan_bytes]: the entropy-coded bytes of the batch, concatenated (what lies between two segments,
+ * such as an RSTn, is not read). seg[n_seg][5] int32: byte offset, byte length, first MCU, MCU count, frame index of every segment (a restart interval, or
+ * the whole scan of a frame without DRI), the segments of a frame contiguous and the frames in order; frame_seg[T + 1]: the
+ * first segment of every frame (frame_seg[T] = n_seg); max_segs_per_frame: the largest difference. ftab[T]: table blocks.
+ * -> coef[T][my][mx][bpm][64] int16 in zigzag order (zeroed by a memset on the stream first; only non-zero values are stored)
+ * and status[n_seg]. One lane decodes one segment: FF 00 -> FF, DC prediction from 0, ZRL, EOB. It reads no byte outside its
+ * segment (beyond the end bits read as 1s), writes only its own MCUs, and stops with a status at the first error.
+ * replaces scripts/evaluation/funcs.py:154-169, :188-190 (decord's get_batch: the entropy stage) */
+int dc_jpeg_decode_entropy(const uint8_t* scan, int64_t scan_bytes, const int32_t* seg, const int32_t* frame_seg,
+                           const uint8_t* ftab, int16_t* coef, int32_t* status, int n_seg, int T, int my, int mx, int ncomp, int hs,
+                           int vs, int max_segs_per_frame, void* stream);
+
+/* coef -> sample planes uint8 padded to whole MCUs, per frame Y [my 8 vs][mx 8 hs] followed (ncomp = 3) by Cb and Cr
+ * [my 8][mx 8]. fp32: coefficient x table entry, separable 8x8 inverse DCT with the orthonormal matrix the encoder uses, + 128,
+ * floor(v + 0.5), clamp to 0..255.
+ * replaces scripts/evaluation/funcs.py:154-169, :188-190 (decord's get_batch: the transform stage) */
+int dc_jpeg_decode_idct(const int16_t* coef, const uint8_t* ftab, uint8_t* planes, int T, int my, int mx, int ncomp, int hs, int vs,
+                        void* stream);
+
+/* planes -> out: uint8 [T][H][W][3] (planar = 0) or fp32 [T][3][H][W] holding the same integers (planar = 1). Chroma is
+ * upsampled by the triangle filter (per doubled axis 3/4 of the nearer and 1/4 of the farther sample, edges replicate, only the
+ * ceil(H / vs) x ceil(W / hs) real samples are read); R = Y + 1.402 (Cr - 128), G = Y - 0.344136286 (Cb - 128) - 0.714136286
+ * (Cr - 128), B = Y + 1.772 (Cb - 128); floor(v + 0.5), clamp. Grey writes Y to all three channels.
+ * replaces scripts/evaluation/funcs.py:154-169, :188-190 (decord's get_batch: the output stage) */
+int dc_jpeg_decode_output(const uint8_t* planes, void* out, int T, int H, int W, int ncomp, int hs, int vs, int planar,
+                          void* stream);
+
 /* ---- animated GIF (GIF89a, one global colour table of up to 256 entries, LZW minimum code size 8) ----
  * Together the four entries stand where the reference hands its uint8 frames to a video encoder
  * (torchvision.io.write_video: utils/save_video.py:27-43, scripts/evaluation/inference.py:115-162) and where its guidance
