@@ -7,24 +7,24 @@
 //   (double-buffered, next tile's loads issued before the MFMA block). Scores are computed transposed,
 //   S^T = K Q^T with v_mfma_f32_32x32x16_bf16, so a lane owns one query row: the softmax max/sum are per-lane
 //   scalars and the S^T accumulator is, after exp2 and bf16 packing, directly the B operand of O^T += V^T P^T
-//   (k order permuted as the accumulator layout dictates; V^T fragments come from ds_read_b64_tr_b16).
+//   (k order permuted as the accumulator layout dictates; V^T fragments come from ds_read_b64_tr_b16). attn_parts.h states
+//   which lane holds what and has the pieces the kernels of this scheme share.
 //
 // dc_temporal_attn_d64: attention across the T<=16 frames of one spatial position (one wave per
 //   (clip, position, head)); reference: TemporalTransformer.forward attention.py:365-412 -> CrossAttention :81-144.
 #include "dc_common.h"
 #include "dcrafter_hip.h"
+#include "attn_parts.h"
 #include "lds_stage.h"
 #include <stdlib.h>
 #include <type_traits>
 
 namespace {
 
-constexpr int V_LD = 192;  // bytes per V row in LDS: 4 consecutive rows land on 4 distinct 64-byte bank quarters
-
 constexpr int FA_BQ = 128;   // query rows per workgroup
 constexpr int FA_BKV = 64;   // keys per tile
 constexpr int FA_KBYTES = FA_BKV * 128;
-constexpr int FA_VBYTES = FA_BKV * V_LD;
+constexpr int FA_VBYTES = FA_BKV * ATTN_VLD;
 constexpr int FA_STAGE = FA_KBYTES + FA_VBYTES;
 
 // QB = 32-row query blocks per wave. QB = 2 reads every K / V fragment from LDS once for two query blocks: at QB = 1
@@ -57,7 +57,7 @@ __global__ __launch_bounds__(256, 2) void flash_attn_d64_kernel(
     const bf16_t* vb = v + (size_t)b * kv_bstride * ldv + head * 64;
     bf16_t* ob = o + (size_t)b * q_bstride * ldo + head * 64;
 
-    // ---- Q fragments (B operand): lane (r, h) holds Q[row][16kk + 8h .. +7] for each of its QB query blocks
+    // ---- Q fragments (B operand, pre-scaled) for each of the wave's QB query blocks
     int qrow[QB];
     bf16x8_t qf[QB][4];
 #pragma unroll
@@ -66,14 +66,8 @@ __global__ __launch_bounds__(256, 2) void flash_attn_d64_kernel(
         const int qc = qrow[x] < Lq ? qrow[x] : Lq - 1;
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
-            // Q is pre-multiplied by scale*log2(e) (one extra bf16 rounding of Q, the size of the one it already has):
-            // the scores then leave the MFMA in exp2 units and, with the accumulator started at -m, as s - m directly
             const u32x4_t raw = *reinterpret_cast<const u32x4_t*>(qb + (size_t)qc * ldq + kk * 16 + fh * 8);
-            u32x4_t sc;
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                sc[e] = pack_bf2(__uint_as_float(raw[e] << 16) * c, __uint_as_float(raw[e] & 0xffff0000u) * c);
-            qf[x][kk] = __builtin_bit_cast(bf16x8_t, sc);
+            qf[x][kk] = attn_q_scaled(raw, c);
         }
     }
 
@@ -95,20 +89,17 @@ __global__ __launch_bounds__(256, 2) void flash_attn_d64_kernel(
         char* sk = smem + buf * FA_STAGE;
         char* sv = sk + FA_KBYTES;
 #pragma unroll
-        for (int i = 0; i < 2; ++i) {
+        for (int i = 0; i < 2; ++i) {                     // attn_stage_row, by hand (profiles/attn_parts_isa.txt)
             const int r = srow + 32 * i;
             *reinterpret_cast<u32x4_t*>(sk + lds_off128(r, chunk)) = kreg[i];
-            *reinterpret_cast<u32x4_t*>(sv + r * V_LD + chunk * 16) = vreg[i];
+            *reinterpret_cast<u32x4_t*>(sv + r * ATTN_VLD + chunk * 16) = vreg[i];
         }
     };
 
     f32x16_t oacc[QB][2];
     f32x16_t ofin[DUAL ? QB : 1][2];  // DUAL: normalised text result (+ scaled image result)
     float m_run[QB], l_run[QB];       // m_run: running row max in exp2 units (0 until the first tile sets it)
-    // per-lane byte offset of the transposed V read inside a 4-row block: lane i of a 16-lane group supplies
-    // row (i>>2), columns 4*(i&3).. of the 16-column block ((lane>>4)&1)
-    const int li = lane & 15;
-    const int tr_off = (li >> 2) * V_LD + (((lane >> 4) & 1) * 16 + (li & 3) * 4) * 2;
+    const int tr_off = attn_vt_lane_off(lane);
 #pragma unroll 1
     for (int pass = 0; pass < (DUAL ? 2 : 1); ++pass) {
     if (DUAL && pass == 1) {          // second key/value set; the LDS ring is free (the tile loop ends on a barrier)
@@ -161,10 +152,8 @@ __global__ __launch_bounds__(256, 2) void flash_attn_d64_kernel(
 #pragma unroll
                 for (int jb = 0; jb < 2; ++jb)
 #pragma unroll
-                    for (int r = 0; r < 16; ++r) {
-                        const int j = t * FA_BKV + jb * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-                        if (j >= Lk) s[x][jb][r] = -1e30f;
-                    }
+                    for (int r = 0; r < 16; ++r)
+                        if (attn_key_of(t * FA_BKV + jb * 32, r, fh) >= Lk) s[x][jb][r] = -1e30f;
         }
         // online softmax: this lane owns one query row per block; its partner (lane ^ 32) holds the other keys
 #pragma unroll
@@ -213,20 +202,14 @@ __global__ __launch_bounds__(256, 2) void flash_attn_d64_kernel(
                 const int jbase = jb * 32 + 16 * ks + 4 * fh;
                 bf16x8_t pf[QB];          // P fragments are packed right before use: S registers die here
 #pragma unroll
-                for (int x = 0; x < QB; ++x) {
-                    u32x4_t pw;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) pw[e] = pack_bf2(s[x][jb][8 * ks + 2 * e], s[x][jb][8 * ks + 2 * e + 1]);
-                    pf[x] = __builtin_bit_cast(bf16x8_t, pw);
-                }
+                for (int x = 0; x < QB; ++x) pf[x] = attn_pack_p(s[x][jb], ks);
 #pragma unroll
                 for (int db = 0; db < 2; ++db) {
-                    const char* vp = sv + jbase * V_LD + db * 64 + tr_off;
+                    // attn_vt_frag, the reads by hand (profiles/attn_parts_isa.txt)
+                    const char* vp = sv + jbase * ATTN_VLD + db * 64 + tr_off;
                     const bf16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4_t*)(vp));
-                    const bf16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4_t*)(vp + 8 * V_LD));
-                    bf16x8_t vf;
-                    vf[0] = lo[0]; vf[1] = lo[1]; vf[2] = lo[2]; vf[3] = lo[3];
-                    vf[4] = hi[0]; vf[5] = hi[1]; vf[6] = hi[2]; vf[7] = hi[3];
+                    const bf16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4_t*)(vp + 8 * ATTN_VLD));
+                    const bf16x8_t vf = attn_vt_join(lo, hi);
 #pragma unroll
                     for (int x = 0; x < QB; ++x)
                         oacc[x][db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[x], oacc[x][db], 0, 0, 0);
@@ -278,23 +261,9 @@ __global__ __launch_bounds__(256, 2) void flash_attn_d64_kernel(
                     }
             }
         } else {
-            // a row's channels 8 qd .. 8 qd + 7 are split over its two lanes: one v_permlane32_swap per dword between the
-            // groups qd and qd + 1 turns eight 8-byte stores per row block into four 16-byte ones (issue-bound store tail; with
-            // 93 keys the epilogue is a large part of a cross-attention workgroup)
             bf16_t* orow = ob + (size_t)(qrow[x] < Lq ? qrow[x] : Lq - 1) * ldo;
-#pragma unroll
-            for (int db = 0; db < 2; ++db)
-#pragma unroll
-                for (int qd = 0; qd < 4; qd += 2) {
-                    unsigned a0 = pack_bf2(oacc[x][db][4 * qd + 0] * inv, oacc[x][db][4 * qd + 1] * inv);
-                    unsigned a1 = pack_bf2(oacc[x][db][4 * qd + 2] * inv, oacc[x][db][4 * qd + 3] * inv);
-                    unsigned b0 = pack_bf2(oacc[x][db][4 * qd + 4] * inv, oacc[x][db][4 * qd + 5] * inv);
-                    unsigned b1 = pack_bf2(oacc[x][db][4 * qd + 6] * inv, oacc[x][db][4 * qd + 7] * inv);
-                    const auto r0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
-                    const auto r1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-                    u32x4_t pk = {r0[0], r1[0], r0[1], r1[1]};
-                    if (qrow[x] < Lq) *reinterpret_cast<u32x4_t*>(orow + db * 32 + 8 * (qd + fh)) = pk;
-                }
+            const f32x16_t fin[2] = {oacc[x][0] * inv, oacc[x][1] * inv};
+            attn_store_row(orow, qrow[x] < Lq, fh, fin);
         }
     }
 }
@@ -307,10 +276,9 @@ __global__ __launch_bounds__(256, 2) void flash_attn_d64_kernel(
 // K / V through the L2 -> CU path for 32 KB of q and o - and ran the level-0 launches at 1.9 TB/s of q + o. Here a query tile
 // costs its own bytes only, the next tile's q is requested before the current one is computed, and there is no barrier in the
 // loop. All keys of a set are visible at once, so the softmax is a plain two-pass one (max, then exp and sum): no running state.
-// 64 < Lk <= 96, Lk2 <= 32 (dc_cross_attn_dual_d64 keeps the general kernel for anything else). Same fragment scheme as above:
-// S^T = K (cQ)^T so a lane owns a query row; the packed S^T accumulator is the B operand of O^T += V^T P^T; V^T via tr reads.
+// 64 < Lk <= 96, Lk2 <= 32 (dc_cross_attn_dual_d64 keeps the general kernel for anything else). The fragment scheme of attn_parts.h.
 constexpr int XA_QT_MAX = 8;                                // query tiles of 128 rows per workgroup: chosen per launch (below)
-constexpr int XA_K1 = 0, XA_V1 = 96 * 128, XA_K2 = XA_V1 + 96 * V_LD, XA_V2 = XA_K2 + 32 * 128, XA_LDS = XA_V2 + 32 * V_LD;
+constexpr int XA_K1 = 0, XA_V1 = 96 * 128, XA_K2 = XA_V1 + 96 * ATTN_VLD, XA_V2 = XA_K2 + 32 * 128, XA_LDS = XA_V2 + 32 * ATTN_VLD;
 
 __global__ __launch_bounds__(256, 2) void cross_attn_resident_kernel(
     const bf16_t* __restrict__ q, const bf16_t* __restrict__ k, const bf16_t* __restrict__ v, const bf16_t* __restrict__ k2,
@@ -348,16 +316,10 @@ __global__ __launch_bounds__(256, 2) void cross_attn_resident_kernel(
             vr[3] = *reinterpret_cast<const u32x4_t*>(vb2 + (size_t)j * ldkv + chunk * 8);
         }
 #pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            const int r = srow + 32 * i;
-            *reinterpret_cast<u32x4_t*>(smem + XA_K1 + lds_off128(r, chunk)) = kr[i];
-            *reinterpret_cast<u32x4_t*>(smem + XA_V1 + r * V_LD + chunk * 16) = vr[i];
-        }
-        *reinterpret_cast<u32x4_t*>(smem + XA_K2 + lds_off128(srow, chunk)) = kr[3];
-        *reinterpret_cast<u32x4_t*>(smem + XA_V2 + srow * V_LD + chunk * 16) = vr[3];
+        for (int i = 0; i < 3; ++i) attn_stage_row(smem + XA_K1, smem + XA_V1, srow + 32 * i, chunk, kr[i], vr[i]);
+        attn_stage_row(smem + XA_K2, smem + XA_V2, srow, chunk, kr[3], vr[3]);
     }
-    const int li = lane & 15;
-    const int tr_off = (li >> 2) * V_LD + (((lane >> 4) & 1) * 16 + (li & 3) * 4) * 2;
+    const int tr_off = attn_vt_lane_off(lane);
 
     const int row0 = qg * (qt * 128) + wave * 32 + fr;              // this lane's query row in tile 0
     auto load_q = [&](int tile, u32x4_t (&raw)[4]) __attribute__((always_inline)) {
@@ -385,10 +347,8 @@ __global__ __launch_bounds__(256, 2) void cross_attn_resident_kernel(
         }
         // keys past the set's length (only the last block can hold any)
 #pragma unroll
-        for (int r = 0; r < 16; ++r) {
-            const int j = (NB - 1) * 32 + (r & 3) + 8 * (r >> 2) + 4 * fh;
-            if (j >= nkeys) s[NB - 1][r] = -1e30f;
-        }
+        for (int r = 0; r < 16; ++r)
+            if (attn_key_of((NB - 1) * 32, r, fh) >= nkeys) s[NB - 1][r] = -1e30f;
         float mx = s[0][0];
 #pragma unroll
         for (int jb = 0; jb < NB; ++jb)
@@ -414,18 +374,10 @@ __global__ __launch_bounds__(256, 2) void cross_attn_resident_kernel(
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
                 const int jbase = jb * 32 + 16 * ks + 4 * fh;
-                u32x4_t pw;
-#pragma unroll
-                for (int e = 0; e < 4; ++e) pw[e] = pack_bf2(s[jb][8 * ks + 2 * e], s[jb][8 * ks + 2 * e + 1]);
-                const bf16x8_t pf = __builtin_bit_cast(bf16x8_t, pw);
+                const bf16x8_t pf = attn_pack_p(s[jb], ks);
 #pragma unroll
                 for (int db = 0; db < 2; ++db) {
-                    const char* vp = sv + jbase * V_LD + db * 64 + tr_off;
-                    const bf16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4_t*)(vp));
-                    const bf16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4_t*)(vp + 8 * V_LD));
-                    bf16x8_t vf;
-                    vf[0] = lo[0]; vf[1] = lo[1]; vf[2] = lo[2]; vf[3] = lo[3];
-                    vf[4] = hi[0]; vf[5] = hi[1]; vf[6] = hi[2]; vf[7] = hi[3];
+                    const bf16x8_t vf = attn_vt_frag((const lds_char_t*)(sv + jbase * ATTN_VLD + db * 64 + tr_off));
                     oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf, oacc[db], 0, 0, 0);
                 }
             }
@@ -436,16 +388,9 @@ __global__ __launch_bounds__(256, 2) void cross_attn_resident_kernel(
     for (int tile = 0; tile < n_tiles; ++tile) {
         const int qrow = row0 + tile * 128;
         if (qg * (qt * 128) + tile * 128 >= Lq) break;              // workgroup-uniform: no rows left in this group
-        // Q fragments (B operand), pre-multiplied by scale*log2(e): the scores leave the MFMA in exp2 units
-        bf16x8_t qf[4];
+        bf16x8_t qf[4];                                             // Q fragments (B operand, pre-scaled)
 #pragma unroll
-        for (int kk = 0; kk < 4; ++kk) {
-            u32x4_t sc;
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                sc[e] = pack_bf2(__uint_as_float(qraw[kk][e] << 16) * c, __uint_as_float(qraw[kk][e] & 0xffff0000u) * c);
-            qf[kk] = __builtin_bit_cast(bf16x8_t, sc);
-        }
+        for (int kk = 0; kk < 4; ++kk) qf[kk] = attn_q_scaled(qraw[kk], c);
         if (tile + 1 < n_tiles) load_q(tile + 1, qraw);             // next tile's rows (clamped): in flight under this tile
         f32x16_t s[3], o1[2], o2[2];
 #pragma unroll
@@ -457,23 +402,9 @@ __global__ __launch_bounds__(256, 2) void cross_attn_resident_kernel(
         const float l2 = scores(smem + XA_K2, Lk2, ic<1>{}, s, qf);
         pv_mma(smem + XA_V2, ic<1>{}, s, o2);
         const float w1 = 1.0f / l1, w2 = acc_scale / l2;
-        // store: a row's channels 8 qd .. 8 qd + 7 are split over its two lanes; one v_permlane32_swap per dword between the
-        // groups qd and qd + 1 gives each lane 16 contiguous bytes
         bf16_t* orow = ob + (size_t)(qrow < Lq ? qrow : Lq - 1) * ldo;
-#pragma unroll
-        for (int db = 0; db < 2; ++db)
-#pragma unroll
-            for (int qd = 0; qd < 4; qd += 2) {
-                float f[8];
-#pragma unroll
-                for (int e = 0; e < 8; ++e) f[e] = w1 * o1[db][4 * qd + e] + w2 * o2[db][4 * qd + e];
-                const unsigned a0 = pack_bf2(f[0], f[1]), a1 = pack_bf2(f[2], f[3]);
-                const unsigned b0 = pack_bf2(f[4], f[5]), b1 = pack_bf2(f[6], f[7]);
-                const auto r0 = __builtin_amdgcn_permlane32_swap(a0, b0, false, false);
-                const auto r1 = __builtin_amdgcn_permlane32_swap(a1, b1, false, false);
-                u32x4_t pk = {r0[0], r1[0], r0[1], r1[1]};
-                if (qrow < Lq) *reinterpret_cast<u32x4_t*>(orow + db * 32 + 8 * (qd + fh)) = pk;
-            }
+        const f32x16_t fin[2] = {w1 * o1[0] + w2 * o2[0], w1 * o1[1] + w2 * o2[1]};
+        attn_store_row(orow, qrow < Lq, fh, fin);
     }
 }
 
@@ -502,7 +433,6 @@ __global__ __launch_bounds__(256) void temporal_attn_d64_kernel(const bf16_t* __
     const size_t row = ((size_t)b * T + t_c) * HW + p;
     const bf16_t* rq = qkv + row * ld + head * 64;
     const bf16_t* rk = rq + C;
-    const bf16_t* rv = rq + 2 * C;
 
     // fragments: A = K[t'=t16][d = 32s + 8g ..], B = Q[t=t16][same d]
     bf16x8_t kf[2], qf[2];
@@ -523,7 +453,6 @@ __global__ __launch_bounds__(256) void temporal_attn_d64_kernel(const bf16_t* __
         *reinterpret_cast<uint4*>(sv + vr * 128 + vc * 2) = a;
         *reinterpret_cast<uint4*>(sv + vr * 128 + vc * 2 + 16) = bq;
     }
-    (void)rv;
     f32x4_t s4 = {0.f, 0.f, 0.f, 0.f};
     s4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[0], qf[0], s4, 0, 0, 0);
     s4 = __builtin_amdgcn_mfma_f32_16x16x32_bf16(kf[1], qf[1], s4, 0, 0, 0);

@@ -36,6 +36,7 @@
 // and a workgroup streams W1 + W2 (2.4 MB) per 128 rows: with one wave per SIMD issuing the 60 MFMAs, ~260 vector
 // instructions and 15 LDS-DMA pieces of a chunk the kernel is instruction-issue-bound at about half the MFMA rate
 // (DESIGN.md section 3.2 has the per-phase stamps).
+#include "attn_parts.h"
 #include "dc_common.h"
 #include "dcrafter_hip.h"
 #include "lds_stage.h"
@@ -884,11 +885,10 @@ void norm_linear_kernel(const LlParams p) {
 // as X fragments (norm_linear_kernel), the weight streams through LDS head by head (q, k, v: 6 chunks of 32 columns).
 // The q and k blocks never leave registers: in accumulator layout a lane holds 16 of the 32 channels of ITS row, which
 // is an MFMA operand fragment once both factors agree on the k order - S^T = K Q^T is 4 MFMAs on the packed accumulators.
-// v goes through a wave-private LDS patch (transposed reads, as the flash kernel reads V^T); a 32 x 32 score block holds
+// v goes through a wave-private LDS patch (transposed reads: the fragment scheme of attn_parts.h); a 32 x 32 score block holds
 // the two positions' 16 x 16 problems on its diagonal, the rest is masked. bf16 roundings are where the three-kernel
 // path has them (q, k, v, P), the softmax is fp32.
-constexpr int TA_VLD = 192;                    // bytes per v row in the patch (flash kernel's V_LD)
-constexpr int TA_PATCH = 32 * TA_VLD;          // 6 KB per wave: v [32 rows][64 d], then the output rows of the head
+constexpr int TA_PATCH = 32 * ATTN_VLD;        // 6 KB per wave: v [32 rows][64 d], then the output rows of the head
 constexpr int ta_ring(int kh) { return kh == 1 ? 2 : 4; }      // weight stages in LDS (dim 640 runs one workgroup per CU: nobody else
                                                                 // covers the L2 latency of a stage, so it is requested three stages ahead)
 constexpr int ta_lds(int kh) { return ta_ring(kh) * LW_STAGE + 4 * TA_PATCH + 2 * FD * kh * 4; }
@@ -948,8 +948,7 @@ void ln_qkv_tattn_kernel(const TaParams p) {
     ln_rows_inplace<KD>(xf, lns, lns + KD, p.ln_eps, fh);
 
     constexpr int PD = 6;
-    const int li = lane & 15;
-    const int tr_off = (li >> 2) * TA_VLD + (((lane >> 4) & 1) * 16 + (li & 3) * 4) * 2;      // transposed v read (flash kernel)
+    const int tr_off = attn_vt_lane_off(lane);
     const int px = fr >> 4;                                       // which of the wave's two positions this lane's row is
     for (int h = h_begin; h < h_end; ++h) {
         bf16x8_t qf[4], kf[4];
@@ -989,11 +988,8 @@ void ln_qkv_tattn_kernel(const TaParams p) {
                 // q / k block of this row: the two operand fragments of k steps 2 (part & 1), + 1
 #pragma unroll
                 for (int s2 = 0; s2 < 2; ++s2) {
-                    u32x4_t pw;
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) pw[e] = pack_bf2(acc[8 * s2 + 2 * e], acc[8 * s2 + 2 * e + 1]);
-                    if (part < 2) qf[2 * (part & 1) + s2] = __builtin_bit_cast(bf16x8_t, pw);
-                    else kf[2 * (part & 1) + s2] = __builtin_bit_cast(bf16x8_t, pw);
+                    if (part < 2) qf[2 * (part & 1) + s2] = attn_pack_p(acc, s2);
+                    else kf[2 * (part & 1) + s2] = attn_pack_p(acc, s2);
                 }
             } else {
                 // v block -> the wave's patch, row-major [frame row][64 d]: channels 8 q + 4 fh + i of half (part & 1)
@@ -1002,7 +998,7 @@ void ln_qkv_tattn_kernel(const TaParams p) {
                     uint2 pk;
                     pk.x = pack_bf2(acc[4 * q], acc[4 * q + 1]);
                     pk.y = pack_bf2(acc[4 * q + 2], acc[4 * q + 3]);
-                    *reinterpret_cast<uint2*>(vpatch + fr * TA_VLD + (32 * (part & 1) + 8 * q + 4 * fh) * 2) = pk;
+                    *reinterpret_cast<uint2*>(vpatch + fr * ATTN_VLD + (32 * (part & 1) + 8 * q + 4 * fh) * 2) = pk;
                 }
             }
         }
@@ -1012,7 +1008,7 @@ void ln_qkv_tattn_kernel(const TaParams p) {
         for (int r = 0; r < 16; ++r) sc[r] = 0.f;
 #pragma unroll
         for (int j = 0; j < 4; ++j) sc = __builtin_amdgcn_mfma_f32_32x32x16_bf16(kf[j], qf[j], sc, 0, 0, 0);
-        // lane = query row fr; sc[r] = score of key row n = (r & 3) + 8 (r >> 2) + 4 fh: the same position iff (r >> 3) == px
+        // lane = query row fr; sc[r] = score of key row attn_key_of(0, r, fh): the same position iff (r >> 3) == px
         float mx = -1e30f;
 #pragma unroll
         for (int r = 0; r < 16; ++r) {
@@ -1031,7 +1027,7 @@ void ln_qkv_tattn_kernel(const TaParams p) {
         bf16x8_t pf[2];
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) {
-            u32x4_t pw;
+            u32x4_t pw;                              // attn_pack_p with the normalisation folded in
 #pragma unroll
             for (int e = 0; e < 4; ++e) pw[e] = pack_bf2(sc[8 * ks + 2 * e] * inv, sc[8 * ks + 2 * e + 1] * inv);
             pf[ks] = __builtin_bit_cast(bf16x8_t, pw);
@@ -1045,12 +1041,7 @@ void ln_qkv_tattn_kernel(const TaParams p) {
             for (int r = 0; r < 16; ++r) oacc[db][r] = 0.f;
 #pragma unroll
             for (int ks = 0; ks < 2; ++ks) {
-                const char* vp = vpatch + (16 * ks + 4 * fh) * TA_VLD + db * 64 + tr_off;
-                const bf16x4_t lo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4_t*)(vp));
-                const bf16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4_t*)(vp + 8 * TA_VLD));
-                bf16x8_t vf;
-                vf[0] = lo[0]; vf[1] = lo[1]; vf[2] = lo[2]; vf[3] = lo[3];
-                vf[4] = hi[0]; vf[5] = hi[1]; vf[6] = hi[2]; vf[7] = hi[3];
+                const bf16x8_t vf = attn_vt_frag((const lds_char_t*)(vpatch + (16 * ks + 4 * fh) * ATTN_VLD + db * 64 + tr_off));
                 oacc[db] = __builtin_amdgcn_mfma_f32_32x32x16_bf16(vf, pf[ks], oacc[db], 0, 0, 0);
             }
         }

@@ -36,18 +36,18 @@
 // in/out operands (hipcc had hoisted v_accvgpr_read of the row sums above a plain s_nop statement).
 // S lives in architectural VGPRs (the exp / max stream reads it), O, l and Q in the accumulator file.
 // K / V tiles of 64 keys: global -> registers -> LDS ring of 4 stages, one barrier per tile; K fragments by ds_read_b128
-// (XOR-swizzled rows), V^T fragments by ds_read_b64_tr_b16.
+// (XOR-swizzled rows), V^T fragments by ds_read_b64_tr_b16. The fragment scheme is that of attn_parts.h.
 #include "dc_common.h"
 #include "dcrafter_hip.h"
+#include "attn_parts.h"
 #include "lds_stage.h"
 #include <type_traits>
 #include <stdlib.h>
 
 namespace {
 
-constexpr int FP_VLD = 192;                 // bytes per V row in LDS (4 consecutive rows on 4 distinct 64-byte bank quarters)
 constexpr int FP_KBYTES = 64 * 128;
-constexpr int FP_VBYTES = 64 * FP_VLD;
+constexpr int FP_VBYTES = 64 * ATTN_VLD;
 constexpr int FP_STAGE = FP_KBYTES + FP_VBYTES;     // 20 KB
 constexpr int FP_NSTAGE = 4;
 constexpr int FP_RING = FP_NSTAGE * FP_STAGE;       // 80 KB
@@ -117,7 +117,7 @@ void flash_attn_d64_pipe_kernel(const bf16_t* __restrict__ q, const bf16_t* __re
     const bf16_t* vb = v + (size_t)b * kv_bstride * ldv + head * 64;
     bf16_t* ob = o + (size_t)b * q_bstride * ldo + head * 64;
 
-    // ---- Q fragments (B operand of S^T = K (cQ)^T): lane (r, h) holds cQ[row][16kk + 8h .. +7] of its query blocks
+    // ---- Q fragments (B operand, pre-scaled) of the wave's query blocks
     int qrow[QB];
     bf16x8_t Q[QB][4];
 #pragma unroll
@@ -126,14 +126,8 @@ void flash_attn_d64_pipe_kernel(const bf16_t* __restrict__ q, const bf16_t* __re
         const int qc = qrow[x] < Lq ? qrow[x] : Lq - 1;
 #pragma unroll
         for (int kk = 0; kk < 4; ++kk) {
-            // Q is pre-multiplied by scale*log2(e) (one more bf16 rounding of Q, the size of the one it already has): the
-            // scores leave the MFMA in exp2 units
             const u32x4_t raw = *reinterpret_cast<const u32x4_t*>(qb + (size_t)qc * ldq + kk * 16 + fh * 8);
-            u32x4_t sc;
-#pragma unroll
-            for (int e = 0; e < 4; ++e)
-                sc[e] = pack_bf2(__uint_as_float(raw[e] << 16) * c, __uint_as_float(raw[e] & 0xffff0000u) * c);
-            Q[x][kk] = __builtin_bit_cast(bf16x8_t, sc);
+            Q[x][kk] = attn_q_scaled(raw, c);
             asm volatile("" : "+a"(Q[x][kk]));        // lives in the accumulator file from here on (B operand only)
         }
     }
@@ -156,27 +150,25 @@ void flash_attn_d64_pipe_kernel(const bf16_t* __restrict__ q, const bf16_t* __re
         else kreg[j >> 1] = __builtin_amdgcn_raw_buffer_load_b128(krs, kgo, row0 * 2 * ldk, 0);
 #endif
     };
-    // per-lane LDS store offsets inside a stage (K rows XOR-swizzled by 16-byte chunk - the swizzle of row r + 32 is that of row
-    // r -, V rows padded to FP_VLD): rows 32.. are immediates
-    const unsigned kso = (unsigned)(srow * 128 + ((chunk ^ ((srow >> 1) & 7)) << 4));
-    const unsigned vso = (unsigned)(FP_KBYTES + srow * FP_VLD + chunk * 16);
+    // per-lane LDS store offsets inside a stage (attn_stage_row's; the swizzle of K row r + 32 is that of row r): rows 32.. are
+    // immediates
+    const unsigned kso = (unsigned)lds_off128(srow, chunk);
+    const unsigned vso = (unsigned)(FP_KBYTES + srow * ATTN_VLD + chunk * 16);
     auto store_piece = [&](int stage, int j) __attribute__((always_inline)) {
         char* sk = smem + stage * FP_STAGE;
 #ifndef FP_DBG_NOSTORE
-        if (j & 1) *reinterpret_cast<u32x4_t*>(sk + vso + (j >> 1) * 32 * FP_VLD) = vreg[j >> 1];
+        if (j & 1) *reinterpret_cast<u32x4_t*>(sk + vso + (j >> 1) * 32 * ATTN_VLD) = vreg[j >> 1];
         else *reinterpret_cast<u32x4_t*>(sk + kso + (j >> 1) * 4096) = kreg[j >> 1];
 #endif
     };
 
     // ---- per-lane LDS offsets of the fragment reads
-    // K fragment kk of a 32-key half tile (rows 32 PAR + fr): 16-byte chunk (2 kk + fh) ^ ((fr >> 1) & 7) of the row
+    // K fragment kk of a 32-key half tile (rows 32 PAR + fr): 16-byte chunk 2 kk + fh of the row
     int koff[4];
 #pragma unroll
-    for (int kk = 0; kk < 4; ++kk) koff[kk] = fr * 128 + (((kk * 2 + fh) ^ ((fr >> 1) & 7)) << 4);
-    // V^T fragment: lane i of a 16-lane group supplies row (i >> 2), columns 4 (i & 3).. of the 16-column block
-    // ((lane >> 4) & 1); keys 4 fh + (i >> 2) of a 16-key k step (+ 8 for the high half of the fragment)
-    const int li = lane & 15;
-    const int voff = FP_KBYTES + (4 * fh + (li >> 2)) * FP_VLD + (((lane >> 4) & 1) * 16 + (li & 3) * 4) * 2;
+    for (int kk = 0; kk < 4; ++kk) koff[kk] = lds_off128(fr, kk * 2 + fh);
+    // V^T fragment: keys 4 fh .. of a 16-key k step
+    const int voff = FP_KBYTES + 4 * fh * ATTN_VLD + attn_vt_lane_off(lane);
     const unsigned lds0 = (unsigned)(uintptr_t)((const lds_char_t*)smem);
 
     // ---- state
@@ -199,15 +191,12 @@ void flash_attn_d64_pipe_kernel(const bf16_t* __restrict__ q, const bf16_t* __re
     bf16x4_t vlo;
     auto rd_v_half = [&](int idx, unsigned addr, int par) __attribute__((always_inline)) {      // idx = 4 ks + 2 db + (0 lo, 1 hi)
         const int ks = idx >> 2, db = (idx >> 1) & 1;
-        const lds_char_t* vp = (const lds_char_t*)(uintptr_t)addr + (par * 32 + 16 * ks) * FP_VLD + db * 64;
+        const lds_char_t* vp = (const lds_char_t*)(uintptr_t)addr + (par * 32 + 16 * ks) * ATTN_VLD + db * 64;
         if (!(idx & 1)) {
             vlo = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4_t*)(vp));
         } else {
-            const bf16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4_t*)(vp + 8 * FP_VLD));
-            bf16x8_t f;
-            f[0] = vlo[0]; f[1] = vlo[1]; f[2] = vlo[2]; f[3] = vlo[3];
-            f[4] = hi[0]; f[5] = hi[1]; f[6] = hi[2]; f[7] = hi[3];
-            Vf[ks][db] = f;
+            const bf16x4_t hi = __builtin_amdgcn_ds_read_tr16_b64_v4i16((lds_bf16x4_t*)(vp + 8 * ATTN_VLD));
+            Vf[ks][db] = attn_vt_join(vlo, hi);
         }
     };
 
@@ -229,12 +218,8 @@ void flash_attn_d64_pipe_kernel(const bf16_t* __restrict__ q, const bf16_t* __re
 #pragma unroll
                 for (int e = 0; e < 16; ++e) { O[x][0][e] *= alpha; O[x][1][e] *= alpha; L[x][e] *= alpha; }
 #pragma unroll
-                for (int ks = 0; ks < 2; ++ks)
-#pragma unroll
-                    for (int e = 0; e < 4; ++e) {
-                        const unsigned w = Pp[x][ks][e];
-                        Pp[x][ks][e] = pack_bf2(__uint_as_float(w << 16) * alpha, __uint_as_float(w & 0xffff0000u) * alpha);
-                    }
+                for (int ks = 0; ks < 2; ++ks)               // 8 bf16 times alpha
+                    Pp[x][ks] = __builtin_bit_cast(u32x4_t, attn_q_scaled(Pp[x][ks], alpha));
             }
 #pragma unroll
             for (int e = 0; e < 16; ++e) Sp[x][e] -= step;
@@ -505,10 +490,8 @@ void flash_attn_d64_pipe_kernel(const bf16_t* __restrict__ q, const bf16_t* __re
 #pragma unroll
     for (int x = 0; x < QB; ++x) {
         const float inv = 1.0f / l_tot[x];
-        // a row's 8 channels 8 qd .. 8 qd + 7 are split over its two lanes (fh = 0 / 1: 4 each). One v_permlane32_swap per
-        // dword between the groups qd and qd + 1 gives the lower lane the 16 contiguous bytes of group qd and the upper lane
-        // those of group qd + 1: 4 16-byte stores per row block instead of 8 8-byte ones (the store tail is issue-bound)
         bf16_t* orow = ob + (size_t)(qrow[x] < Lq ? qrow[x] : Lq - 1) * ldo;
+        // attn_store_row, by hand: every spelling of the call moved instructions of this kernel (profiles/attn_parts_isa.txt)
 #pragma unroll
         for (int db = 0; db < 2; ++db)
 #pragma unroll

@@ -132,6 +132,44 @@ def test_gemm_parts_are_spelled_once():
     assert "tt < p.T) mk |= 1 << t" in pipe
 
 
+def test_attn_parts_are_spelled_once():
+    """One spelling of the fragment scheme of the 32x32x16 attention kernels (csrc/attn_parts.h): the pre-scaled Q fragment,
+    the lane offset of the transposed V read, the two transposed reads 8 V rows apart, the permlane-swap store, and one V row
+    pitch. Named exemptions, each because every shared spelling moved instructions between the kernel's MFMAs or grew its
+    registers (profiles/attn_parts_isa.txt): flash_attn_d64_kernel (attention.hip) reads its V^T fragment and stages its K / V
+    rows by hand; flash_attn_d64_pipe_kernel (flash_pipe.hip) issues the two reads of a V^T fragment in different gaps of its
+    schedule (rd_v_half) and keeps its store epilogue."""
+    def code(path):
+        text = open(path).read()
+        return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+    files = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".h")))
+    assert "attn_parts.h" in files and len(files) > 10
+    src = {f: code(os.path.join(CSRC, f)) for f in files}
+    count = lambda pattern: {f: n for f in files if (n := len(re.findall(pattern, src[f])))}
+    # 8 bf16 times one scalar, rounded to bf16 again: the Q pre-scale (and the pipe kernel's rescale of the packed P, through it)
+    assert count(r"<< 16\) \* (\w+), __uint_as_float\([^()]* & 0xffff0000u\) \* \1\)") == {"attn_parts.h": 1}
+    # lane -> offset of its transposed V read
+    assert count(r"\(\(\(lane >> 4\) & 1\) \* 16 \+ \(\w+ & 3\) \* 4\) \* 2") == {"attn_parts.h": 1}
+    # the read 8 V rows further on
+    assert count(r"\+ 8 \* \w*VLD\b") == {"attn_parts.h": 1, "attention.hip": 1, "flash_pipe.hip": 1}
+    att, fp = src["attention.hip"], src["flash_pipe.hip"]
+    k0, k1 = att.index("void flash_attn_d64_kernel("), att.index("void cross_attn_resident_kernel(")
+    assert k0 < att.index("+ 8 * ATTN_VLD") < k1
+    assert fp.index("auto rd_v_half") < fp.index("+ 8 * ATTN_VLD") < fp.index("auto rescale")
+    # K / V row staging: lds_off128 for K, the pitch for V
+    assert count(r"\w+ \* ATTN_VLD \+ chunk \* 16") == {"attn_parts.h": 1, "attention.hip": 1, "flash_pipe.hip": 1}
+    assert att.index("auto store_tile") < att.index("* ATTN_VLD + chunk * 16") < att.index("f32x16_t oacc[QB][2]")
+    assert "vso = (unsigned)(FP_KBYTES + srow * ATTN_VLD + chunk * 16)" in fp       # an offset for its own stores, kept in a register
+    # the permlane-swap store
+    assert count(r"permlane32_swap") == {"attn_parts.h": 2, "flash_pipe.hip": 2}
+    assert fp.index("row_sums();") < fp.index("permlane32_swap") and fp.count("void flash_attn_d64_pipe_kernel(") == 1
+    # one pitch, one name
+    for f in ("attention.hip", "flash_pipe.hip", "ff_fused.hip"):
+        assert not re.search(r"\b(V_LD|FP_VLD|TA_VLD)\b", src[f]), f
+        assert not re.search(r"\b192\b", src[f]), f
+    assert len(re.findall(r"\b192\b", src["attn_parts.h"])) == 1
+
+
 def _tiny_model(config_name, extra=None):
     from dynamicrafter_amd.utils.utils import instantiate_from_config
     from tests.golden_cfg import TINY_AE, TINY_UNET

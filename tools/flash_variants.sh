@@ -7,10 +7,11 @@ CS="$ROOT/dynamicrafter_amd/csrc"
 OUT="$ROOT/tools/_variants"
 mkdir -p "$OUT"
 FLAGS="--offload-arch=gfx950 -O3 -std=c++17 -fPIC -I$ROOT/include -I$CS"
+SRCS="$(grep '^SRCS=' "$CS/build.sh" | cut -d'"' -f2)"      # the product's files: their objects (build.sh) are linked as they are
 build() {  # name, extra flags
   /opt/rocm/bin/hipcc $FLAGS $2 -c "$CS/flash_pipe.hip" -o "$OUT/flash_pipe_$1.o"
   OBJS=""
-  for f in gemm_conv gemm_conv_glds ff_fused norms attention elementwise encoders runtime; do OBJS="$OBJS $CS/$f.o"; done
+  for f in $SRCS; do [ "$f" = flash_pipe ] || OBJS="$OBJS $CS/$f.o"; done
   /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT/libdc_$1.so" $OBJS "$OUT/flash_pipe_$1.o"
   rm -f "$OUT/flash_pipe_$1.o"
 }
@@ -38,9 +39,9 @@ for v in "$@"; do
     x16_*) # tool builds of flash_pipe16.hip: x16_nolds, x16_nostage, x16_noex, x16_nolds_nostage, x16_mfma
       fl=""; case "$v" in *nolds*) fl="$fl -DF16_DBG_NOLDS";; esac; case "$v" in *nostage*) fl="$fl -DF16_DBG_NOSTAGE";; esac
       case "$v" in *noex*) fl="$fl -DF16_DBG_NOEX";; esac; case "$v" in *mfma*) fl="-DF16_DBG_NOLDS -DF16_DBG_NOSTAGE -DF16_DBG_NOEX";; esac
-      /opt/rocm/bin/hipcc $FLAGS $fl -c "$CS/flash_pipe16.hip" -o "$OUT/fp16_$v.o"
+      /opt/rocm/bin/hipcc $FLAGS $fl -c "$ROOT/tools/experimental/flash_pipe16.hip" -o "$OUT/fp16_$v.o"
       OBJS=""
-      for f in gemm_conv gemm_conv_glds ff_fused norms attention flash_pipe elementwise encoders runtime; do OBJS="$OBJS $CS/$f.o"; done
+      for f in $SRCS; do OBJS="$OBJS $CS/$f.o"; done
       /opt/rocm/bin/hipcc --offload-arch=gfx950 -shared -fPIC -o "$OUT/libdc_$v.so" $OBJS "$OUT/fp16_$v.o"
       rm -f "$OUT/fp16_$v.o" ;;
     *) echo "unknown variant $v"; exit 1 ;;

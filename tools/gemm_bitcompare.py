@@ -218,6 +218,45 @@ def child(out_dir):
     json.dump(index, open(os.path.join(out_dir, "index.json"), "w"))
 
 
+def run_children(script, other_lib, timeout, tmp, env_sets=(("", {}),)):
+    """Runs `script --child <dir>` once per library ("this": the tree's, "other": other_lib through DC_HIP_LIB) and per named
+    environment set (a set with a name gets `--env-set <name>` too), each in a fresh process. -> {"this": dir, "other": dir}, or
+    None when a child failed: nothing more runs on the GPU after that."""
+    dirs = {}
+    for tag, lib in (("this", None), ("other", os.path.abspath(other_lib))):
+        dirs[tag] = os.path.join(tmp, tag)
+        os.mkdir(dirs[tag])
+        for name, extra in env_sets:
+            env = dict(os.environ)
+            env.pop("DC_HIP_LIB", None)
+            if lib:
+                env["DC_HIP_LIB"] = lib
+            env.update(extra)
+            r = subprocess.run([sys.executable, os.path.abspath(script), "--child", dirs[tag]] + (["--env-set", name] if name else []),
+                               env=env, timeout=timeout, stdout=subprocess.DEVNULL)
+            if r.returncode != 0:
+                print(f"the run on the {tag} library ended with status {r.returncode}", file=sys.stderr)
+                return None
+    return dirs
+
+
+def compare_saved(dirs, index="index.json"):
+    """The outputs two children saved as <dir>/<i:03d>.pt with an index of dict(name, shape, label) -> (lines, number that
+    differ, labels reached, equal count of cases): one line per case, equal = same label and torch.equal."""
+    import torch
+    ia, ib = (json.load(open(os.path.join(dirs[t], index))) for t in ("this", "other"))
+    lines, differ, reached = [], 0, set()
+    for i, (ca, cb) in enumerate(zip(ia, ib)):
+        a, b = (torch.load(os.path.join(dirs[t], f"{i:03d}.pt")) for t in ("this", "other"))
+        same = ca["label"] == cb["label"] and torch.equal(a, b)
+        differ += not same
+        reached.add(ca["label"])
+        label = ca["label"] if ca["label"] == cb["label"] else f"{ca['label']} != {cb['label']}"
+        lines.append(f"{ca['name']} {tuple(ca['shape'])} {label} {'equal' if same else 'DIFFERENT'}")
+    lines.append(f"{len(ia)} outputs, {differ} differ")
+    return lines, differ, reached, len(ia) == len(ib)
+
+
 def main():
     ap = argparse.ArgumentParser(description=__doc__, formatter_class=argparse.RawDescriptionHelpFormatter)
     ap.add_argument("--other-lib", help="the library to compare this tree's against (selected through DC_HIP_LIB)")
@@ -229,33 +268,13 @@ def main():
         return child(args.child)
     if not args.other_lib or not os.path.exists(args.other_lib):
         ap.error("--other-lib: no such file")
-    import torch
     tmp = tempfile.mkdtemp(prefix="gemm_bitcompare_")
     try:
-        dirs = {}
-        for tag, lib in (("this", None), ("other", os.path.abspath(args.other_lib))):
-            dirs[tag] = os.path.join(tmp, tag)
-            os.mkdir(dirs[tag])
-            env = dict(os.environ)
-            env.pop("DC_HIP_LIB", None)
-            if lib:
-                env["DC_HIP_LIB"] = lib
-            r = subprocess.run([sys.executable, os.path.abspath(__file__), "--child", dirs[tag]], env=env, timeout=args.timeout,
-                               stdout=subprocess.DEVNULL)
-            if r.returncode != 0:                  # nothing more runs on the GPU after a child that failed
-                print(f"the run on the {tag} library ended with status {r.returncode}", file=sys.stderr)
-                return 2
-        ia, ib = (json.load(open(os.path.join(dirs[t], "index.json"))) for t in ("this", "other"))
-        lines, differ, reached = [], 0, set()
-        for i, (ca, cb) in enumerate(zip(ia, ib)):
-            a, b = (torch.load(os.path.join(dirs[t], f"{i:03d}.pt")) for t in ("this", "other"))
-            same = ca["label"] == cb["label"] and torch.equal(a, b)
-            differ += not same
-            reached.add(ca["label"])
-            label = ca["label"] if ca["label"] == cb["label"] else f"{ca['label']} != {cb['label']}"
-            lines.append(f"{ca['name']} {tuple(ca['shape'])} {label} {'equal' if same else 'DIFFERENT'}")
+        dirs = run_children(__file__, args.other_lib, args.timeout, tmp)
+        if dirs is None:
+            return 2
+        lines, differ, reached, same_count = compare_saved(dirs)
         want = source_labels()
-        lines.append(f"{len(ia)} outputs, {differ} differ")
         lines.append(f"labels reached ({len(reached & want)} of the {len(want)} that dc_note_variant call sites produce):")
         lines += [f"  {l}" for l in sorted(reached)]
         missing = sorted(want - reached)
@@ -264,7 +283,7 @@ def main():
         sys.stdout.write(text)
         if args.listing:
             open(args.listing, "w").write(text)
-        return 1 if differ or missing or len(ia) != len(ib) else 0
+        return 1 if differ or missing or not same_count else 0
     finally:
         shutil.rmtree(tmp, ignore_errors=True)
 
