@@ -123,6 +123,9 @@ SIGNATURES = {
     "dc_gif_map": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _P]),
     "dc_gif_lzw": (_I, [_P, _P, _P, _I, _I, _I, _L, _P]),
     "dc_gif_pack": (_I, [_P, _P, _P, _P, _P, _I, _I, _L, _L, _P]),
+    "dc_png_filter": (_I, [_P, _P, _I, _I, _I, _I, _P]),
+    "dc_png_deflate": (_I, [_P, _P, _P, _P, _I, _I, _I, _L, _P]),
+    "dc_png_pack": (_I, [_P, _P, _P, _P, _P, _P, _I, _I, _I, _L, _L, _P]),
     "dc_prep_resize_h":(_I, [_P, _P, _P, _P, _P] + [_I] * 8 + [_P]),
     "dc_prep_finish": (_I, [_P, _P, _P, _P, _P] + [_I] * 15 + [_P]),
     "dc_resize_f32_h": (_I, [_P, _P, _P, _P, _P] + [_I] * 10 + [_P]),

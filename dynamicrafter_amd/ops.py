@@ -1119,6 +1119,73 @@ def gif_pack(scratch, chunk_bits, chunk_off, out, frame_len, *, T, chunks_per_fr
     return out
 
 
+# ---------------------------------------------------------------------------------------------- PNG / APNG (csrc/png.hip)
+PNG_CHUNK = 16384                               # DC_PNG_CHUNK: bytes of a frame's scanlines per independently coded chunk
+PNG_CHUNK_LIMIT = 65535                         # DC_PNG_CHUNK_LIMIT: LEN of a stored block is 16 bits
+
+
+def png_chunk_max_bytes(n):
+    """DC_PNG_CHUNK_MAX_BYTES(n): the worst-case string of a chunk of n bytes (the stored form, n + 5), in whole 32-bit words."""
+    return (n + 5 + 3) // 4 * 4
+
+
+def png_frame_max_bytes(N, chunk):
+    """DC_PNG_FRAME_MAX_BYTES(N, chunk): 78 01, every chunk of a plane of N bytes in the stored form, Adler-32."""
+    return 6 + N + 5 * ((N + chunk - 1) // chunk)
+
+
+def png_filter(frames, planes):
+    """frames uint8 [T, H, W, C] (C in 1, 3, 4) -> planes uint8 [T, H, 1 + W C]: per row the filter type 0..4 with the least sum of
+    min(r, 256 - r) over its residuals (the lowest type on a tie) and the residuals."""
+    _flat(frames, torch.uint8, "frames"); _flat(planes, torch.uint8, "planes")
+    if frames.dim() != 4 or frames.shape[3] not in (1, 3, 4):
+        raise ValueError(f"png_filter: frames [T, H, W, 1|3|4] expected, got {tuple(frames.shape)}")
+    T, H, W, Cc = frames.shape
+    if min(T, H, W) < 1 or H * (1 + W * Cc) > 0x7FFFFFFF:
+        raise ValueError(f"png_filter: frames of {H} x {W} x {Cc} x {T}")
+    _need(planes, T * H * (1 + W * Cc), "planes")
+    _launch("png_filter", 0.0, 2.0 * frames.numel(), _hip.lib().dc_png_filter, _ptr(frames), _ptr(planes), T, H, W, Cc, stream_ptr())
+    return planes
+
+
+def png_deflate(planes, scratch, chunk_len, chunk_adler, *, T, N, chunk, stride):
+    """planes uint8 [T, N] -> scratch uint8 [n_chunks, stride], chunk_len int32 [n_chunks] (bytes), chunk_adler int32 [n_chunks]
+    (the Adler-32 of the chunk alone, as a bit pattern); n_chunks = T ceil(N / chunk)."""
+    _flat(planes, torch.uint8, "planes"); _flat(scratch, torch.uint8, "scratch")
+    _flat(chunk_len, torch.int32, "chunk_len"); _flat(chunk_adler, torch.int32, "chunk_adler")
+    if min(T, N, chunk) < 1 or chunk > PNG_CHUNK_LIMIT or N > 0x7FFFFFFF:
+        raise ValueError(f"png_deflate: T {T}, N {N}, chunk {chunk}")
+    n_chunks = T * ((N + chunk - 1) // chunk)
+    if stride % 4 or stride < png_chunk_max_bytes(min(chunk, N)):
+        raise ValueError(f"png_deflate: stride {stride} is no multiple of 4 or below the worst case of {min(chunk, N)} bytes")
+    if scratch.data_ptr() % 4:
+        raise ValueError("png_deflate: scratch must be 4-byte aligned")
+    _need(planes, T * N, "planes"); _need(scratch, n_chunks * stride, "scratch")
+    _need(chunk_len, n_chunks, "chunk_len"); _need(chunk_adler, n_chunks, "chunk_adler")
+    _launch("png_deflate", 0.0, float(T * N), _hip.lib().dc_png_deflate, _ptr(planes), _ptr(scratch), _ptr(chunk_len),
+            _ptr(chunk_adler), T, N, chunk, stride, stream_ptr())
+    return n_chunks
+
+
+def png_pack(scratch, chunk_len, chunk_adler, chunk_off, out, frame_len, *, T, N, chunk, stride, frame_stride):
+    """scratch [T ceil(N / chunk), stride] + chunk_len + chunk_adler -> out uint8 [T, frame_stride] (one zlib stream per frame),
+    frame_len int32 [T]; chunk_off int32 [T ceil(N / chunk)] is workspace."""
+    _flat(scratch, torch.uint8, "scratch"); _flat(out, torch.uint8, "out")
+    for t, name in ((chunk_len, "chunk_len"), (chunk_adler, "chunk_adler"), (chunk_off, "chunk_off"), (frame_len, "frame_len")):
+        _flat(t, torch.int32, name)
+    if min(T, N, chunk, stride, frame_stride) < 1 or T > 65535 or chunk > PNG_CHUNK_LIMIT:
+        raise ValueError(f"png_pack: T {T}, N {N}, chunk {chunk}, stride {stride}, frame_stride {frame_stride}")
+    cpf = (N + chunk - 1) // chunk
+    if 6 + cpf * stride > 0x7FFFFFFF:
+        raise ValueError(f"png_pack: {cpf} chunks of {stride} bytes pass 2^31 in a frame")
+    n = T * cpf
+    _need(scratch, n * stride, "scratch"); _need(chunk_len, n, "chunk_len"); _need(chunk_adler, n, "chunk_adler")
+    _need(chunk_off, n, "chunk_off"); _need(out, T * frame_stride, "out"); _need(frame_len, T, "frame_len")
+    _launch("png_pack(2 kernels)", 0.0, 0.0, _hip.lib().dc_png_pack, _ptr(scratch), _ptr(chunk_len), _ptr(chunk_adler), _ptr(chunk_off),
+            _ptr(out), _ptr(frame_len), T, N, chunk, stride, frame_stride, stream_ptr())
+    return out
+
+
 # ---------------------------------------------------------------------------------------------- image -> clip (csrc/preprocess.hip)
 RESIZE_PRECISION_BITS = 22                      # Pillow's PRECISION_BITS for 8-bit channels (32 - 8 - 2)
 

@@ -196,14 +196,15 @@ def load_image_batch(filepath_list, image_size=(256, 256), device=None):
     return torch.stack(batch_tensor, dim=0)
 
 
-def save_videos(batch_tensors, savedir, filenames, fps=10, container="avi", quality=90):
+def save_videos(batch_tensors, savedir, filenames, fps=10, container="avi", quality=90, deflate=None):
     """funcs.py:206-218: batch_tensors [b, n_samples, c, t, h, w] on the device -> one clip per batch entry, its n_samples side
     by side (clamp, (v + 1) / 2, x 255, uint8: dc_frames_to_u8), written as <savedir>/<filenames[idx]>.<ext>. The reference writes
     h264 `.mp4`; here the extension follows `container`: "avi" (Motion-JPEG at JPEG `quality`, the default), "apng" (.png) or
-    "gif". Returns the paths written (the reference returns nothing)."""
+    "gif". `deflate` ("zlib", "hip" or None = the environment's DC_PNG_DEFLATE) picks the compressor of "apng". Returns the paths
+    written (the reference returns nothing)."""
     from ...utils.save_video import _write_clip, frames_to_uint8
     paths = []
     for idx, vid_tensor in enumerate(batch_tensors):
         grid = frames_to_uint8(vid_tensor)                                     # [t, h, n * w, c]
-        paths.append(_write_clip(os.path.join(savedir, f"{filenames[idx]}"), grid, fps, container, quality))
+        paths.append(_write_clip(os.path.join(savedir, f"{filenames[idx]}"), grid, fps, container, quality, deflate=deflate))
     return paths

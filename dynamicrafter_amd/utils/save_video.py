@@ -8,6 +8,14 @@ torchvision.io.write_video (h264, crf 10); no h264 encoder exists in this image,
 (animated PNG: lossless, zlib only, one file per clip, plays in browsers) and single frames as PNG. File names keep the
 reference's stems; only the extension changes (.png instead of .mp4).
 
+The PNG writers take `deflate=`: "zlib" is the host path (the frames travel to the CPU, zlib level 6 on filter-0 scanlines, frame
+after frame) and what they do when nothing is said; "hip" keeps the frames on the GPU: per row the PNG filter with the least
+sum of absolute residuals, then every 16 KiB of scanlines deflated on their own into whole bytes - run-length matches, one
+dynamic-Huffman block, or a stored block where that is not shorter - and packed behind 78 01 with the Adler-32 combined from the
+chunks (csrc/png.hip: filter, deflate of one chunk per wave, pack). Only the zlib streams travel to the host, which adds the chunk
+framing and the CRCs. `deflate=None` reads the environment variable DC_PNG_DEFLATE (so the generate command line reaches the HIP
+path without a new flag) and falls back to "zlib". DESIGN.md 4.10.
+
 `container="avi"` writes a video file instead: Motion-JPEG in an AVI container. The frames are encoded as baseline JPEG
 (T.81 SOF0, YCbCr 4:2:0, Annex K tables scaled by `quality` as libjpeg does, restart intervals) by three HIP launches on
 the uint8 frames where they lie (csrc/jpeg.hip: coefficients, entropy coding of one restart segment per wave, pack); only the
@@ -46,7 +54,7 @@ def frames_to_uint8(video):
     return out
 
 
-# ---------------------------------------------------------------------------------------------- PNG / APNG (zlib only)
+# ---------------------------------------------------------------------------------------------- PNG / APNG (zlib, or csrc/png.hip)
 def _chunk(tag, data):
     return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
 
@@ -65,25 +73,103 @@ def _scanlines(frame, level):
     return zlib.compress(raw.tobytes(), level)
 
 
-def write_png(path, frame, level=6):
-    """frame: uint8 [h, w, c] (c in 1, 3, 4), numpy or tensor."""
-    f = np.ascontiguousarray(frame.cpu().numpy() if isinstance(frame, torch.Tensor) else frame)
-    if f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] not in (1, 3, 4):
-        raise ValueError(f"write_png: uint8 [h, w, 1|3|4] expected, got {f.dtype} {f.shape}")
+_PNG_SCRATCH_BYTES = 256 << 20           # deflate scratch per batch of frames (worst-case sized rows)
+
+
+def png_deflate_mode(deflate=None):
+    """"zlib" (the host compressor on filter-0 scanlines) or "hip" (csrc/png.hip); None reads the environment variable
+    DC_PNG_DEFLATE and falls back to "zlib"."""
+    if deflate is None:
+        deflate = os.environ.get("DC_PNG_DEFLATE") or "zlib"
+    if deflate not in ("zlib", "hip"):
+        raise ValueError(f"deflate must be 'zlib' or 'hip', got {deflate!r}")
+    return deflate
+
+
+def encode_png_frames(frames_u8, chunk=None):
+    """frames_u8: uint8 [t, h, w, c] on the GPU (what frames_to_uint8 returns; c in 1, 3, 4) -> list of t zlib streams (bytes), the
+    payload of an IDAT / fdAT chunk each. Lossless: adaptive row filters, then every `chunk` bytes of scanlines (default
+    ops.PNG_CHUNK, at most 65535) deflated on their own with run-length matches and dynamic Huffman tables, or stored where that is
+    not shorter. Three launches per batch of frames and one device-to-host copy of the packed streams."""
+    if not isinstance(frames_u8, torch.Tensor) or not frames_u8.is_cuda:
+        raise RuntimeError("encode_png_frames runs on the HIP path only (deflate='zlib' is the host path)")
+    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] not in (1, 3, 4):
+        raise ValueError(f"encode_png_frames: uint8 [t, h, w, 1|3|4] expected, got {frames_u8.dtype} {tuple(frames_u8.shape)}")
+    f = frames_u8.contiguous()
+    t, h, w, c = f.shape
+    N = h * (1 + w * c)
+    if t < 1 or h < 1 or w < 1 or N > 0x7FFFFFFF:
+        raise ValueError(f"encode_png_frames: frames of {h} x {w} x {c} x {t}")
+    chunk = ops.PNG_CHUNK if chunk is None else int(chunk)
+    if not 1 <= chunk <= ops.PNG_CHUNK_LIMIT:
+        raise ValueError(f"chunk must be in 1..{ops.PNG_CHUNK_LIMIT} bytes, got {chunk}")
+    dev = f.device
+    cpf = (N + chunk - 1) // chunk
+    stride = ops.png_chunk_max_bytes(min(chunk, N))
+    frame_stride = ops.png_frame_max_bytes(N, chunk)
+    tb = max(1, min(t, 65535, _PNG_SCRATCH_BYTES // (cpf * stride)))     # frames per batch
+    planes = torch.empty(tb * N, dtype=torch.uint8, device=dev)
+    scratch = torch.empty(tb * cpf * stride, dtype=torch.uint8, device=dev)
+    chunk_len, chunk_adler, chunk_off = (torch.empty(tb * cpf, dtype=torch.int32, device=dev) for _ in range(3))
+    frame_len = torch.empty(tb, dtype=torch.int32, device=dev)
+    out = torch.empty(tb * frame_stride, dtype=torch.uint8, device=dev)
+    streams = []
+    for t0 in range(0, t, tb):
+        n = min(tb, t - t0)
+        ops.png_filter(f[t0:t0 + n], planes)
+        ops.png_deflate(planes, scratch, chunk_len, chunk_adler, T=n, N=N, chunk=chunk, stride=stride)
+        ops.png_pack(scratch, chunk_len, chunk_adler, chunk_off, out, frame_len, T=n, N=N, chunk=chunk, stride=stride,
+                     frame_stride=frame_stride)
+        lens = frame_len[:n].cpu().tolist()
+        if max(lens) > frame_stride:
+            raise RuntimeError(f"encode_png_frames: a frame of {max(lens)} bytes outgrew the worst case {frame_stride}")
+        host = out[:n * frame_stride].view(n, frame_stride)[:, :max(lens)].cpu().numpy()
+        streams += [host[i, :lens[i]].tobytes() for i in range(n)]
+    return streams
+
+
+def _hip_streams(name, frames, ndim):
+    """The zlib streams of deflate="hip" for uint8 [(t,) h, w, c] on the GPU; refuses everything else before a file exists."""
+    if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
+        raise RuntimeError(f"{name}: deflate='hip' needs a CUDA uint8 tensor (deflate='zlib' takes numpy and CPU tensors)")
+    if frames.dtype != torch.uint8 or frames.dim() != ndim or frames.shape[-1] not in (1, 3, 4):
+        raise ValueError(f"{name}: uint8 [{'t, ' if ndim == 4 else ''}h, w, 1|3|4] expected, got {frames.dtype} {tuple(frames.shape)}")
+    return encode_png_frames(frames if ndim == 4 else frames[None])
+
+
+def _png_file(w, h, c, stream):
+    return b"\x89PNG\r\n\x1a\n" + _ihdr(w, h, c) + _chunk(b"IDAT", stream) + _chunk(b"IEND", b"")
+
+
+def write_png(path, frame, level=6, deflate=None):
+    """frame: uint8 [h, w, c] (c in 1, 3, 4), numpy or tensor. `deflate`: "zlib" (zlib at `level` on filter-0 scanlines, on the
+    host), "hip" (encode_png_frames; a CUDA tensor only) or None = png_deflate_mode()."""
+    if png_deflate_mode(deflate) == "hip":
+        stream, = _hip_streams("write_png", frame, 3)
+        shape = frame.shape
+    else:
+        f = np.ascontiguousarray(frame.cpu().numpy() if isinstance(frame, torch.Tensor) else frame)
+        if f.dtype != np.uint8 or f.ndim != 3 or f.shape[2] not in (1, 3, 4):
+            raise ValueError(f"write_png: uint8 [h, w, 1|3|4] expected, got {f.dtype} {f.shape}")
+        stream, shape = _scanlines(f, level), f.shape
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     with open(path, "wb") as fh:
-        fh.write(b"\x89PNG\r\n\x1a\n" + _ihdr(f.shape[1], f.shape[0], f.shape[2]) + _chunk(b"IDAT", _scanlines(f, level))
-                 + _chunk(b"IEND", b""))
+        fh.write(_png_file(shape[1], shape[0], shape[2], stream))
     return path
 
 
-def write_apng(path, frames, fps=8, level=6, loops=0):
+def write_apng(path, frames, fps=8, level=6, loops=0, deflate=None):
     """frames: uint8 [t, h, w, c]. Animated PNG (acTL / fcTL / fdAT): frame 0 doubles as the still image every PNG
-    reader shows; `loops` = 0 repeats forever."""
-    f = np.ascontiguousarray(frames.cpu().numpy() if isinstance(frames, torch.Tensor) else frames)
-    if f.dtype != np.uint8 or f.ndim != 4 or f.shape[3] not in (1, 3, 4):
-        raise ValueError(f"write_apng: uint8 [t, h, w, 1|3|4] expected, got {f.dtype} {f.shape}")
-    t, h, w, c = f.shape
+    reader shows; `loops` = 0 repeats forever. `deflate` as in write_png; the chunk framing is the same for both."""
+    if png_deflate_mode(deflate) == "hip":
+        streams = _hip_streams("write_apng", frames, 4)
+        t, h, w, c = frames.shape
+    else:
+        f = np.ascontiguousarray(frames.cpu().numpy() if isinstance(frames, torch.Tensor) else frames)
+        if f.dtype != np.uint8 or f.ndim != 4 or f.shape[3] not in (1, 3, 4):
+            raise ValueError(f"write_apng: uint8 [t, h, w, 1|3|4] expected, got {f.dtype} {f.shape}")
+        t, h, w, c = f.shape
+        streams = None
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     seq = 0
     with open(path, "wb") as fh:
@@ -91,7 +177,7 @@ def write_apng(path, frames, fps=8, level=6, loops=0):
         for i in range(t):
             fh.write(_chunk(b"fcTL", struct.pack(">IIIIIHHBB", seq, w, h, 0, 0, 1, int(fps), 0, 0)))
             seq += 1
-            data = _scanlines(f[i], level)
+            data = streams[i] if streams is not None else _scanlines(f[i], level)
             if i == 0:
                 fh.write(_chunk(b"IDAT", data))
             else:
@@ -404,10 +490,11 @@ def write_gif(path, frames_u8, fps=8, loops=0, dither=0, chunk=None):
     return path
 
 
-def _write_clip(stem, grid, fps, container, quality, dither=0):
-    """grid uint8 [t, h, w, c] on the GPU -> <stem>.png (APNG), <stem>.avi (Motion-JPEG) or <stem>.gif."""
+def _write_clip(stem, grid, fps, container, quality, dither=0, deflate=None):
+    """grid uint8 [t, h, w, c] on the GPU -> <stem>.png (APNG, compressed as `deflate` says), <stem>.avi (Motion-JPEG) or
+    <stem>.gif."""
     if container == "apng":
-        return write_apng(stem + ".png", grid, fps=fps)
+        return write_apng(stem + ".png", grid, fps=fps, deflate=deflate)
     if container == "avi":
         return write_avi_mjpeg(stem + ".avi", encode_jpeg_frames(grid, quality=quality), grid.shape[2], grid.shape[1], fps)
     if container == "gif":
@@ -416,32 +503,44 @@ def _write_clip(stem, grid, fps, container, quality, dither=0):
 
 
 # ---------------------------------------------------------------------------------------------- reference-named entry points
-def save_results(prompt, samples, filename, fakedir, fps=8, loop=False, container="apng", quality=90, dither=0):
+def save_results(prompt, samples, filename, fakedir, fps=8, loop=False, container="apng", quality=90, dither=0, deflate=None):
     """inference.py:115-137: the batch as ONE clip, its n samples side by side. samples [n, c, t, h, w]. `container`: "apng"
-    (default, lossless), "avi" (Motion-JPEG at JPEG `quality`) or "gif" (256 colours, ordered dither of amplitude `dither`)."""
+    (default, lossless; `deflate` = "zlib", "hip" or None for png_deflate_mode()), "avi" (Motion-JPEG at JPEG `quality`) or "gif"
+    (256 colours, ordered dither of amplitude `dither`)."""
     video = samples[:, :, :-1] if loop else samples            # loop mode drops the duplicated last frame
     grid = frames_to_uint8(video)
-    return _write_clip(os.path.join(fakedir, filename.split(".")[0]), grid, fps, container, quality, dither)
+    return _write_clip(os.path.join(fakedir, filename.split(".")[0]), grid, fps, container, quality, dither, deflate)
 
 
-def save_results_seperate(prompt, samples, filename, fakedir, fps=10, loop=False, container="apng", quality=90, dither=0):
+def save_results_seperate(prompt, samples, filename, fakedir, fps=10, loop=False, container="apng", quality=90, dither=0,
+                          deflate=None):
     """inference.py:140-162: one clip file per sample, under `samples_separate` (name kept as the reference spells it)."""
     video = samples[:, :, :-1] if loop else samples
     out = []
     d = fakedir.replace("samples", "samples_separate")
     for i in range(video.shape[0]):
         grid = frames_to_uint8(video[i:i + 1])
-        out.append(_write_clip(os.path.join(d, f"{filename.split('.')[0]}_sample{i}"), grid, fps, container, quality, dither))
+        out.append(_write_clip(os.path.join(d, f"{filename.split('.')[0]}_sample{i}"), grid, fps, container, quality, dither,
+                               deflate))
     return out
 
 
-def tensor_to_frames(video, savedir, stem="frame", fmt="png", quality=90):
+def tensor_to_frames(video, savedir, stem="frame", fmt="png", quality=90, deflate=None):
     """One still per frame of a [n, c, t, h, w] batch laid out side by side (the still-image twin of tensor_to_mp4,
-    utils/save_video.py:27-43): PNG (default) or, with fmt="jpg", baseline JPEG at `quality`."""
+    utils/save_video.py:27-43): PNG (default; `deflate` as in write_png, "hip" keeps the frames on the device and encodes them
+    in one batch) or, with fmt="jpg", baseline JPEG at `quality`."""
     grid = frames_to_uint8(video)
+    if fmt == "png" and png_deflate_mode(deflate) == "hip":
+        os.makedirs(os.path.abspath(savedir), exist_ok=True)
+        out = []
+        for i, stream in enumerate(encode_png_frames(grid)):
+            out.append(os.path.join(savedir, f"{stem}_{i:04d}.png"))
+            with open(out[-1], "wb") as fh:
+                fh.write(_png_file(grid.shape[2], grid.shape[1], grid.shape[3], stream))
+        return out
     if fmt == "png":
         grid = grid.cpu().numpy()
-        return [write_png(os.path.join(savedir, f"{stem}_{i:04d}.png"), grid[i]) for i in range(grid.shape[0])]
+        return [write_png(os.path.join(savedir, f"{stem}_{i:04d}.png"), grid[i], deflate="zlib") for i in range(grid.shape[0])]
     if fmt != "jpg":
         raise ValueError(f"fmt must be 'png' or 'jpg', got {fmt!r}")
     os.makedirs(os.path.abspath(savedir), exist_ok=True)

@@ -556,6 +556,52 @@ int dc_gif_lzw(const uint8_t* idx, uint8_t* scratch, int32_t* chunk_bits, int T,
 int dc_gif_pack(const uint8_t* scratch, const int32_t* chunk_bits, int32_t* chunk_off, uint8_t* out, int32_t* frame_len, int T,
                 int chunks_per_frame, int64_t stride, int64_t frame_stride, void* stream);
 
+/* ---- PNG / APNG image data (8-bit grey, RGB or RGBA; one zlib stream per frame) ----
+ * Together the three entries stand where the reference hands its uint8 frames to a video encoder
+ * (torchvision.io.write_video: utils/save_video.py:27-43, scripts/evaluation/inference.py:115-162); the host adds the PNG chunk
+ * framing and the chunk CRCs (dynamicrafter_amd/utils/save_video.py, deflate="hip"). None of them allocates or synchronises; all
+ * check their arguments before any launch.
+ * A frame's plane of N = H * (1 + W * C) scanline bytes is cut into chunks of `chunk` bytes (the last may be shorter),
+ * chunks_per_frame = ceil(N / chunk). Every chunk is coded alone into a whole number of bytes: no token refers to a byte in
+ * front of its chunk. Tokens: a maximal run of L equal bytes is one literal, then matches of min(rem, 258) at distance 1 while
+ * rem >= 3, then the 0..2 bytes left as literals. */
+
+#define DC_PNG_CHUNK 16384         /* the default chunk of utils/save_video.py */
+#define DC_PNG_CHUNK_LIMIT 65535   /* LEN of a stored block is 16 bits */
+/* Upper bound of one chunk's string: the stored form, 5 bytes of block header and the n bytes themselves; a dynamic block is
+ * taken only where it is shorter. Rounded up to whole 32-bit words (whole words of a string are stored as words). */
+#define DC_PNG_CHUNK_MAX_BYTES(n) (((n) + 5LL + 3) / 4 * 4)
+/* Upper bound of a frame's stream: 78 01, every chunk in the stored form, Adler-32. */
+#define DC_PNG_FRAME_MAX_BYTES(N, chunk) (6LL + (N) + 5LL * (((N) + (chunk) - 1LL) / (chunk)))
+
+/* frames[T][H][W][C] uint8 (C = 1, 3, 4) -> planes[T][H][1 + W*C]: per row a filter type byte 0..4 (None, Sub, Up, Average, Paeth
+ * of the PNG specification, bpp = C) and the row's residuals. Filters read the raw bytes of the row and the row above (zeros above
+ * row 0 of every frame). The type with the least sum over the row of min(r, 256 - r) of its residual bytes r wins, the lowest
+ * type on a tie. H * (1 + W*C) < 2^31.
+ * replaces utils/save_video.py:27-43, scripts/evaluation/inference.py:115-162 (the encoder's prediction stage) */
+int dc_png_filter(const uint8_t* frames, uint8_t* planes, int T, int H, int W, int C, void* stream);
+
+/* planes[T][N] (any bytes) -> per chunk its string scratch[n_chunks][stride], its length in bytes chunk_len[n_chunks] and the
+ * Adler-32 of its bytes alone chunk_adler[n_chunks] (A | B << 16), n_chunks = T * ceil(N / chunk), frames in order. A string is
+ * (a) one dynamic-Huffman block with BFINAL 0 (canonical codes of at most 15 bits over the chunk's literal/length counts with
+ * end-of-block counted once; one distance code of length 1, or a single zero length if the chunk has no match; code lengths sent
+ * as runs with 16 / 17 / 18 under a code of at most 7 bits) followed by an empty stored block, which carries BFINAL in the
+ * frame's last chunk, or (b) one stored block; (b) exactly when (a) is not shorter. Bytes behind a string's length are not
+ * written. scratch 4-byte aligned (else DC_ERR_ARG); 1 <= chunk <= DC_PNG_CHUNK_LIMIT; stride a multiple of 4 and >=
+ * DC_PNG_CHUNK_MAX_BYTES(min(chunk, N)), else DC_ERR_SHAPE.
+ * replaces utils/save_video.py:27-43, scripts/evaluation/inference.py:115-162 (the encoder's entropy stage) */
+int dc_png_deflate(const uint8_t* planes, uint8_t* scratch, int32_t* chunk_len, uint32_t* chunk_adler, int T, int N, int chunk,
+                   int64_t stride, void* stream);
+
+/* Exclusive scan of each frame's chunk lengths behind the two bytes 78 01 into chunk_off[n_chunks] (workspace), a byte copy of
+ * the strings to their offsets, the Adler-32 of the whole plane from the chunks' values (big-endian) behind them:
+ * out[T][frame_stride] holds one zlib stream per frame, frame_len[T] = its length, at most DC_PNG_FRAME_MAX_BYTES(N, chunk). Every
+ * byte has one writer; bytes beyond frame_stride are not written: a frame_len above frame_stride tells the caller to pack again
+ * into wider rows. T <= 65535; 6 + ceil(N / chunk) * stride < 2^31.
+ * replaces utils/save_video.py:27-43, scripts/evaluation/inference.py:115-162 (the encoder's output stage) */
+int dc_png_pack(const uint8_t* scratch, const int32_t* chunk_len, const uint32_t* chunk_adler, int32_t* chunk_off, uint8_t* out,
+                int32_t* frame_len, int T, int N, int chunk, int64_t stride, int64_t frame_stride, void* stream);
+
 /* ---- image -> conditioning clip: Pillow's antialiased bilinear resize, centre crop / zero padding, ToTensor, Normalize ----
  * Together the two entries stand where the reference's loader runs torchvision's Resize(min(video_size)) ->
  * CenterCrop(video_size) -> ToTensor -> Normalize(0.5, 0.5) on a PIL image and repeats the result over the frames
