@@ -85,6 +85,25 @@ def test_gemm_geglu(ops):
     dict(n=2, C=8, Co=64, H=8, W=8, stride=1, pad=1, ups=0),           # Cin padded to 64
 ])
 def test_conv3x3(ops, cfg):
+    _conv3x3(ops, cfg)
+
+
+def _under_plan(ops, plan, fn):
+    """fn() with the GEMM plan set to `plan` (None: whatever is set), restored afterwards"""
+    if plan is None:
+        return fn()
+    lib = ops._hip.lib()
+    prev = lib.dc_gemm_set_plan(plan)
+    assert prev >= 0
+    try:
+        return fn()
+    finally:
+        lib.dc_gemm_set_plan(prev)
+
+
+def _conv3x3(ops, cfg, routes=None):
+    """routes = {plan: kernel name}: the launch is repeated under each plan and must be dispatched to exactly that kernel
+    (dc_gemm_last_variant); None: one launch under the current plan, whichever kernel takes it."""
     n, Cc, Co, H, W = cfg["n"], cfg["C"], cfg["Co"], cfg["H"], cfg["W"]
     x = bf(rnd(n, Cc, H, W, seed=1)); w = rnd(Co, Cc, 3, 3, seed=2, scale=(9 * Cc) ** -0.5); b = rnd(Co, seed=3)
     xr = x.float()
@@ -100,10 +119,13 @@ def test_conv3x3(ops, cfg):
     cp = pw.Cin
     rows = torch.zeros(n * H * W, cp, dtype=torch.bfloat16, device=DEV)
     rows[:, :Cc] = x.permute(0, 2, 3, 1).reshape(-1, Cc).to(DEV)
-    out = torch.empty(n * OH * OW, Co, dtype=torch.bfloat16, device=DEV)
-    ops.gemm(rows, pw, out, conv=dict(IH=H, IW=W, OH=OH, OW=OW, stride=cfg["stride"], pad=cfg["pad"], ups=cfg["ups"]))
-    got = out.float().cpu().reshape(n, OH, OW, Co).permute(0, 3, 1, 2)
-    assert rel_l2(got, ref) < 4e-3
+    for plan, want in (routes or {None: None}).items():
+        out = torch.empty(n * OH * OW, Co, dtype=torch.bfloat16, device=DEV)
+        _under_plan(ops, plan, lambda: ops.gemm(rows, pw, out, conv=dict(IH=H, IW=W, OH=OH, OW=OW, stride=cfg["stride"],
+                                                                         pad=cfg["pad"], ups=cfg["ups"])))
+        assert want is None or _variant(ops) == want, (plan, want, _variant(ops))
+        got = out.float().cpu().reshape(n, OH, OW, Co).permute(0, 3, 1, 2)
+        assert rel_l2(got, ref) < 4e-3
 
 
 # ---- conv_out of the UNet (320 -> 4, fp32 rows) and of the AE decoder (128 -> 3, bf16 rows, N padded to 4): the narrow-N kernel
@@ -476,31 +498,125 @@ def test_softmax_and_vae_sample(ops):
 
 
 # ---- large launches: these shapes take the 256-row LDS-DMA pipeline (gemm_conv_glds.hip) --------------------
+# Which kernel each shape of the tests below is dispatched to (dc_gemm_last_variant, asserted by exact name), per plan: 19 is the
+# default, 0 the documented A/B fallback without the one-wave and ping-pong kernels (3 = 19 without the ping-pong kernel). A test
+# named after a kernel that today's default plan no longer gives its shape runs under both plans; a threshold edit that moves a
+# shape to another kernel fails here instead of silently changing what the test covers. (tests/exact_cases.py has the smallest
+# shape of every variant and the dispatch rules.)
+_T, _G, _P, _PIPE = "gemm_conv_kernel", "gemm_conv_glds_kernel", "gemm_persist_kernel", "gemm_pipe320x16_kernel"
+_P320 = (_P + "<320,residual>", _P + "<320>")               # (bf16 launch with residual + row vector, fp32 launch)
+GEMM_ROUTES = {                                             # (M, N, K) -> {plan: (bf16 launch, fp32 launch)}
+    (25600, 512, 320): {19: (_G + "<256>",) * 2},
+    (20480 + 77, 320, 640): {19: (_T + "<64>",) * 2},       # 81 row tiles: below every large-tile threshold
+    (30000, 448, 192): {19: (_G + "<128>",) * 2},
+    (131072, 64, 64): {19: (_P + "<64>",) * 2},
+    (51200 + 100, 320, 128): {19: (_P + "<64>",) * 2},      # 201 x 5 tiles of 64 columns: the persistent kernel, not the 320-wide tile
+    (25600 + 7, 640, 320): {19: (_G + "<320>",) * 2},
+    (52000, 1280, 64): {19: _P320},
+    (65536 + 50, 512, 320): {19: (_P + "<128>",) * 2},
+    (65536 + 50, 320, 320): {19: (_P + "<64>",) * 2},
+    (140000, 640, 640): {19: _P320},
+    (70000, 448, 64): {19: (_P + "<128>",) * 2},
+    (140000, 320, 320): {19: _P320},
+    (135000, 960, 128): {19: _P320},
+    (18432, 1280, 1280): {19: (_P + "<128>",) * 2},         # 72 x 4 = 288 tiles of 320: the 128-wide persistent kernel (720 tiles)
+    (4608 + 33, 1280, 640): {19: (_T + "<128>",) * 2},
+    (73728, 640, 320): {19: _P320},
+    (10000, 320, 2560): {19: (_PIPE + "+splitk", _G + "<320>+splitk"), 0: (_G + "<320>+splitk",) * 2},
+    (256 * 70, 960, 128): {19: (_P + "<128>",) * 2},
+}
+CONV_ROUTES = {                                             # (n, C, Co, H, W, stride, pad, ups) -> {plan: kernel}
+    (32, 64, 256, 40, 40, 1, 1, 0): {19: _G + "<256,conv>"},
+    (30, 128, 320, 33, 47, 1, 1, 0): {19: _PIPE + "<conv>", 0: _T + "<64>"},
+    (32, 64, 256, 20, 20, 1, 1, 1): {19: _G + "<256,conv>"},
+    (32, 64, 256, 80, 80, 2, 1, 0): {19: _G + "<256,conv>"},
+    (36, 128, 320, 33, 47, 1, 1, 0): {19: _PIPE + "<conv>", 0: _G + "<320,conv>"},
+    (32, 64, 640, 20, 20, 1, 1, 1): {19: _PIPE + "<conv,ups>", 0: _G + "<320,conv>"},
+    (32, 64, 320, 81, 80, 2, 1, 0): {19: _PIPE + "<conv>", 0: _G + "<320,conv>"},
+    (32, 128, 1280, 18, 32, 1, 1, 0): {19: _PIPE + "<conv>+splitk", 0: _G + "<320,conv>+splitk"},
+    (32, 64, 640, 9, 16, 1, 1, 0): {19: _T + "<128>"},
+    (30, 192, 320, 17, 23, 1, 1, 0): {19: _PIPE + "<conv>+splitk", 0: _G + "<320,conv>+splitk"},
+    (32, 64, 640, 18, 16, 1, 1, 1): {19: _G + "<128,conv>"},
+    # named after gemm_persist_kernel<320,conv>, which takes >= 1024 tiles (and only where the one-wave kernel is off): these
+    # 576..588-tile shapes go to the one-wave kernel, or to the 320-wide tile under plan 0; the persistent conv kernel itself is
+    # pinned by test_conv3x3_persistent_residual_rowvec under plan 0 and by the exact cases
+    (16, 128, 320, 96, 96, 1, 1, 0): {19: _PIPE + "<conv>+splitk", 0: _G + "<320,conv>+splitk"},
+    (15, 64, 320, 97, 101, 1, 1, 0): {19: _PIPE + "<conv>", 0: _G + "<320,conv>"},
+    (16, 64, 320, 192, 192, 2, 1, 0): {19: _PIPE + "<conv>", 0: _G + "<320,conv>"},
+    (16, 64, 320, 192, 192, 2, 0, 0): {19: _PIPE + "<conv>", 0: _G + "<320,conv>"},
+    # test_conv3x3_splitk
+    (8, 1280, 1280, 18, 32, 1, 1, 0): {19: _PIPE + "<conv>+splitk", 0: _G + "<320,conv>+splitk"},
+    (32, 1280, 1280, 18, 32, 1, 1, 0): {19: _PIPE + "<conv>+splitk", 0: _G + "<320,conv>+splitk"},
+}
+
+
+def _conv_routes(cfg):
+    return CONV_ROUTES[tuple(cfg[k] for k in ("n", "C", "Co", "H", "W", "stride", "pad", "ups"))]
+
+
+def _geglu_routed(ops, M, dim, inner, routes):
+    """The GEGLU projection [M, dim] -> [M, inner] under each plan of routes = {plan: kernel name}"""
+    x = bf(rnd(M, dim, seed=1)); w = rnd(2 * inner, dim, seed=2, scale=dim ** -0.5); b = rnd(2 * inner, seed=3, scale=0.1)
+    pw = ops.PackedWeight.linear(w, b, DEV)
+    h = x.float() @ bf(w).float().t() + b
+    val, gate = h.chunk(2, dim=-1)
+    ref = val * F.gelu(gate)
+    xd = x.to(DEV)
+    for plan, want in routes.items():
+        out = torch.empty(M, inner, dtype=torch.bfloat16, device=DEV)
+        _under_plan(ops, plan, lambda: ops.gemm(xd, pw, out, geglu=True))
+        assert _variant(ops) == want, (plan, want, _variant(ops))
+        assert rel_l2(out, ref) < 4e-3
+
+
+def _tconv3_routed(ops, B, T, HW, Cc, res, routes, twice=False):
+    """The 3-tap temporal conv (+ residual) under each plan of routes = {plan: kernel name}; None: the current plan, any kernel"""
+    x = bf(rnd(B, Cc, T, HW, 1, seed=1)); w = rnd(Cc, Cc, 3, 1, 1, seed=2, scale=(3 * Cc) ** -0.5); b = rnd(Cc, seed=3)
+    ref = F.conv3d(x.float(), bf(w).float(), b, padding=(1, 0, 0)).permute(0, 2, 3, 4, 1).reshape(-1, Cc)
+    pw = ops.PackedWeight.tconv3(w, b, DEV)
+    rows = x.permute(0, 2, 3, 4, 1).reshape(-1, Cc).contiguous().to(DEV)
+    r = bf(rnd(rows.shape[0], Cc, seed=res)) if res else None
+    if res:
+        ref = bf(ref).float() + r.float()
+        r = r.to(DEV)
+    for plan, want in (routes or {None: None}).items():
+        out = torch.empty_like(rows)
+        _under_plan(ops, plan, lambda: ops.gemm(rows, pw, out, tconv=dict(T=T, HW=HW), residual=r))
+        assert want is None or _variant(ops) == want, (plan, want, _variant(ops))
+        assert rel_l2(out, ref) < 4e-3
+        if twice:
+            out2 = torch.empty_like(rows)
+            _under_plan(ops, plan, lambda: ops.gemm(rows, pw, out2, tconv=dict(T=T, HW=HW), residual=r))
+            assert torch.equal(out, out2)            # fixed summation order: bitwise reproducible
 @pytest.mark.parametrize("M,N,K", [(25600, 512, 320), (20480 + 77, 320, 640), (30000, 448, 192), (131072, 64, 64)])
 def test_gemm_plain_large(ops, M, N, K):
+    _gemm_plain_large(ops, M, N, K, GEMM_ROUTES[(M, N, K)])
+
+
+def _gemm_plain_large(ops, M, N, K, routes=None):
+    """routes = {plan: (kernel of the bf16 launch, kernel of the fp32 launch)}, as for _conv3x3"""
     x = bf(rnd(M, K, seed=1)); w = rnd(N, K, seed=2, scale=K ** -0.5); b = rnd(N, seed=3)
     res = bf(rnd(M, N, seed=4)); rv = rnd(4, N, seed=5)
     pw = ops.PackedWeight.linear(w, b, DEV)
     out = torch.empty(M, N, dtype=torch.bfloat16, device=DEV)
     rpv = (M + 3) // 4
-    ops.gemm(x.to(DEV), pw, out, residual=res.to(DEV), rowvec=rv.to(DEV), rows_per_vec=rpv)
-    ref = x.float() @ bf(w).float().t() + b + rv.repeat_interleave(rpv, 0)[:M]
+    ref32 = x.float() @ bf(w).float().t() + b
+    ref = ref32 + rv.repeat_interleave(rpv, 0)[:M]
     ref = bf(ref).float() + res.float()
-    assert rel_l2(out, ref) < 4e-3
-    out32 = torch.empty(M, N, dtype=torch.float32, device=DEV)
-    ops.gemm(x.to(DEV), pw, out32, alpha=0.25)
-    assert rel_l2(out32, 0.25 * (x.float() @ bf(w).float().t() + b)) < 2e-5
+    xd, resd, rvd = x.to(DEV), res.to(DEV), rv.to(DEV)
+    for plan, want in (routes or {None: (None, None)}).items():
+        out.fill_(7.0)
+        _under_plan(ops, plan, lambda: ops.gemm(xd, pw, out, residual=resd, rowvec=rvd, rows_per_vec=rpv))
+        assert want[0] is None or _variant(ops) == want[0], (plan, want[0], _variant(ops))
+        assert rel_l2(out, ref) < 4e-3
+        out32 = torch.empty(M, N, dtype=torch.float32, device=DEV)
+        _under_plan(ops, plan, lambda: ops.gemm(xd, pw, out32, alpha=0.25))
+        assert want[1] is None or _variant(ops) == want[1], (plan, want[1], _variant(ops))
+        assert rel_l2(out32, 0.25 * ref32) < 2e-5
 
 
 def test_gemm_geglu_large(ops):
-    M, dim, inner = 25600 + 33, 128, 512
-    x = bf(rnd(M, dim, seed=1)); w = rnd(2 * inner, dim, seed=2, scale=dim ** -0.5); b = rnd(2 * inner, seed=3, scale=0.1)
-    pw = ops.PackedWeight.linear(w, b, DEV)
-    out = torch.empty(M, inner, dtype=torch.bfloat16, device=DEV)
-    ops.gemm(x.to(DEV), pw, out, geglu=True)
-    h = x.float() @ bf(w).float().t() + b
-    val, gate = h.chunk(2, dim=-1)
-    assert rel_l2(out, val * F.gelu(gate)) < 4e-3
+    _geglu_routed(ops, 25600 + 33, 128, 512, {19: _P + "<128,geglu>"})        # 101 x 8 = 808 tiles of 64 columns
 
 
 @pytest.mark.parametrize("cfg", [
@@ -510,38 +626,21 @@ def test_gemm_geglu_large(ops):
     dict(n=32, C=64, Co=256, H=80, W=80, stride=2, pad=1, ups=0),       # stride 2
 ])
 def test_conv3x3_large(ops, cfg):
-    test_conv3x3(ops, cfg)
+    _conv3x3(ops, cfg, _conv_routes(cfg))
 
 
 def test_tconv3_large(ops):
-    B, T, HW, Cc = 2, 16, 1601, 256
-    x = bf(rnd(B, Cc, T, HW, 1, seed=1)); w = rnd(Cc, Cc, 3, 1, 1, seed=2, scale=(3 * Cc) ** -0.5); b = rnd(Cc, seed=3)
-    ref = F.conv3d(x.float(), bf(w).float(), b, padding=(1, 0, 0))
-    pw = ops.PackedWeight.tconv3(w, b, DEV)
-    rows = x.permute(0, 2, 3, 4, 1).reshape(-1, Cc).contiguous().to(DEV)
-    res = bf(rnd(rows.shape[0], Cc, seed=9))
-    out = torch.empty_like(rows)
-    ops.gemm(rows, pw, out, tconv=dict(T=T, HW=HW), residual=res.to(DEV))
-    got = out.float().cpu()
-    ref_rows = bf(ref.permute(0, 2, 3, 4, 1).reshape(-1, Cc)).float() + res.float()
-    assert rel_l2(got, ref_rows) < 4e-3
+    _tconv3_routed(ops, 2, 16, 1601, 256, 9, {19: _G + "<256,tconv>"})
 
 
 # ---- 256x320 / 256x256 LDS-DMA tiles (2-stage ring) --------------------------------------------------------
 @pytest.mark.parametrize("M,N,K", [(51200 + 100, 320, 128), (25600 + 7, 640, 320), (52000, 1280, 64)])
 def test_gemm_plain_320_tiles(ops, M, N, K):
-    test_gemm_plain_large(ops, M, N, K)
+    _gemm_plain_large(ops, M, N, K, GEMM_ROUTES[(M, N, K)])
 
 
 def test_gemm_geglu_256_tile(ops):
-    M, dim, inner = 32768 - 19, 128, 512
-    x = bf(rnd(M, dim, seed=1)); w = rnd(2 * inner, dim, seed=2, scale=dim ** -0.5); b = rnd(2 * inner, seed=3, scale=0.1)
-    pw = ops.PackedWeight.linear(w, b, DEV)
-    out = torch.empty(M, inner, dtype=torch.bfloat16, device=DEV)
-    ops.gemm(x.to(DEV), pw, out, geglu=True)
-    h = x.float() @ bf(w).float().t() + b
-    val, gate = h.chunk(2, dim=-1)
-    assert rel_l2(out, val * F.gelu(gate)) < 4e-3
+    _geglu_routed(ops, 32768 - 19, 128, 512, {19: "gemm_pp_kernel<geglu>", 3: _P + "<256,geglu>"})
 
 
 @pytest.mark.parametrize("cfg", [
@@ -550,58 +649,37 @@ def test_gemm_geglu_256_tile(ops):
     dict(n=32, C=64, Co=320, H=81, W=80, stride=2, pad=1, ups=0),
 ])
 def test_conv3x3_320_tiles(ops, cfg):
-    test_conv3x3(ops, cfg)
+    _conv3x3(ops, cfg, _conv_routes(cfg))
 
 
 def test_tconv3_320_tile(ops):
-    B, T, HW, Cc = 2, 16, 1601, 320
-    x = bf(rnd(B, Cc, T, HW, 1, seed=1)); w = rnd(Cc, Cc, 3, 1, 1, seed=2, scale=(3 * Cc) ** -0.5); b = rnd(Cc, seed=3)
-    ref = F.conv3d(x.float(), bf(w).float(), b, padding=(1, 0, 0))
-    pw = ops.PackedWeight.tconv3(w, b, DEV)
-    rows = x.permute(0, 2, 3, 4, 1).reshape(-1, Cc).contiguous().to(DEV)
-    out = torch.empty_like(rows)
-    ops.gemm(rows, pw, out, tconv=dict(T=T, HW=HW))
-    assert rel_l2(out, ref.permute(0, 2, 3, 4, 1).reshape(-1, Cc)) < 4e-3
+    _tconv3_routed(ops, 2, 16, 1601, 320, 0, {19: _G + "<320,tconv>"})
 
 
 # ---- persistent cross-tile pipelined GEMM (mode 0, >= 512 output tiles, K <= 1280) --------------------------
 @pytest.mark.parametrize("M,N,K", [(65536 + 50, 512, 320), (65536 + 50, 320, 320), (140000, 640, 640), (70000, 448, 64)])
 def test_gemm_persistent(ops, M, N, K):
-    test_gemm_plain_large(ops, M, N, K)
+    _gemm_plain_large(ops, M, N, K, GEMM_ROUTES[(M, N, K)])
 
 
 def test_gemm_geglu_persistent(ops):
-    M, dim, inner = 65536 + 21, 320, 640
-    x = bf(rnd(M, dim, seed=1)); w = rnd(2 * inner, dim, seed=2, scale=dim ** -0.5); b = rnd(2 * inner, seed=3, scale=0.1)
-    pw = ops.PackedWeight.linear(w, b, DEV)
-    out = torch.empty(M, inner, dtype=torch.bfloat16, device=DEV)
-    ops.gemm(x.to(DEV), pw, out, geglu=True)
-    h = x.float() @ bf(w).float().t() + b
-    val, gate = h.chunk(2, dim=-1)
-    assert rel_l2(out, val * F.gelu(gate)) < 4e-3
+    _geglu_routed(ops, 65536 + 21, 320, 640, {19: "gemm_pp_kernel<geglu>", 3: _P + "<256,geglu>"})
 
 
 @pytest.mark.parametrize("M,N,K", [(140000, 320, 320), (140000, 640, 640), (135000, 960, 128)])
 def test_gemm_persistent_320(ops, M, N, K):
-    test_gemm_plain_large(ops, M, N, K)
+    _gemm_plain_large(ops, M, N, K, GEMM_ROUTES[(M, N, K)])
 
 
 def test_gemm_geglu_persistent_256(ops):
-    M, dim, inner = 131072 + 21, 128, 512
-    x = bf(rnd(M, dim, seed=1)); w = rnd(2 * inner, dim, seed=2, scale=dim ** -0.5); b = rnd(2 * inner, seed=3, scale=0.1)
-    pw = ops.PackedWeight.linear(w, b, DEV)
-    out = torch.empty(M, inner, dtype=torch.bfloat16, device=DEV)
-    ops.gemm(x.to(DEV), pw, out, geglu=True)
-    h = x.float() @ bf(w).float().t() + b
-    val, gate = h.chunk(2, dim=-1)
-    assert rel_l2(out, val * F.gelu(gate)) < 4e-3
+    _geglu_routed(ops, 131072 + 21, 128, 512, {19: "gemm_pp_kernel<geglu>", 3: _P + "<256,geglu>"})
 
 
 # ---- ragged tile counts for the wide (256 x 320, GEGLU 256 x 256) tiles -------------
 @pytest.mark.parametrize("M,N,K", [(18432, 1280, 1280), (4608 + 33, 1280, 640), (73728, 640, 320), (10000, 320, 2560),
                                     (256 * 70, 960, 128)])
 def test_gemm_ragged_wide(ops, M, N, K):
-    test_gemm_plain_large(ops, M, N, K)
+    _gemm_plain_large(ops, M, N, K, GEMM_ROUTES[(M, N, K)])
 
 
 @pytest.mark.parametrize("cfg", [
@@ -611,32 +689,15 @@ def test_gemm_ragged_wide(ops, M, N, K):
     dict(n=32, C=64, Co=640, H=18, W=16, stride=1, pad=1, ups=1),
 ])
 def test_conv3x3_ragged_wide(ops, cfg):
-    test_conv3x3(ops, cfg)
+    _conv3x3(ops, cfg, _conv_routes(cfg))
 
 
 def test_tconv3_ragged_wide(ops):
-    B, T, HW, Cc = 2, 16, 577, 640
-    x = bf(rnd(B, Cc, T, HW, 1, seed=1)); w = rnd(Cc, Cc, 3, 1, 1, seed=2, scale=(3 * Cc) ** -0.5); b = rnd(Cc, seed=3)
-    ref = F.conv3d(x.float(), bf(w).float(), b, padding=(1, 0, 0))
-    pw = ops.PackedWeight.tconv3(w, b, DEV)
-    rows = x.permute(0, 2, 3, 4, 1).reshape(-1, Cc).contiguous().to(DEV)
-    out = torch.empty_like(rows)
-    ops.gemm(rows, pw, out, tconv=dict(T=T, HW=HW))
-    assert rel_l2(out, ref.permute(0, 2, 3, 4, 1).reshape(-1, Cc)) < 4e-3
-    out2 = torch.empty_like(rows)
-    ops.gemm(rows, pw, out2, tconv=dict(T=T, HW=HW))
-    assert torch.equal(out, out2)            # fixed summation order: bitwise reproducible
+    _tconv3_routed(ops, 2, 16, 577, 640, 0, {19: _T + "<128>"}, twice=True)        # 73 row tiles x 2: below every large-tile threshold
 
 
 def test_gemm_geglu_ragged_wide(ops):
-    M, dim, inner = 18432 + 5, 256, 1280
-    x = bf(rnd(M, dim, seed=1)); w = rnd(2 * inner, dim, seed=2, scale=dim ** -0.5); b = rnd(2 * inner, seed=3, scale=0.1)
-    pw = ops.PackedWeight.linear(w, b, DEV)
-    out = torch.empty(M, inner, dtype=torch.bfloat16, device=DEV)
-    ops.gemm(x.to(DEV), pw, out, geglu=True)
-    h = x.float() @ bf(w).float().t() + b
-    val, gate = h.chunk(2, dim=-1)
-    assert rel_l2(out, val * F.gelu(gate)) < 4e-3
+    _geglu_routed(ops, 18432 + 5, 256, 1280, {19: "gemm_pp_kernel<geglu>", 3: _P + "<256,geglu>"})
 
 
 # ---- split-K plans of the 320-wide tile: few tiles (level 3: every tile cut along K) and a little over one wave
@@ -655,25 +716,21 @@ def test_conv3x3_splitk(ops, cfg, res):
         ref = bf(ref).float() + r.float()
     pw = ops.PackedWeight.conv3x3(w, b, DEV)
     rows = x.permute(0, 2, 3, 1).reshape(-1, C).contiguous().to(DEV)
-    outs = []
-    for _ in range(2):
-        out = torch.empty(n * H * W, Co, dtype=torch.bfloat16, device=DEV)
-        ops.gemm(rows, pw, out, conv=dict(IH=H, IW=W, OH=H, OW=W, stride=1, pad=1, ups=0),
-                 residual=None if r is None else r.to(DEV))
-        outs.append(out)
-    assert rel_l2(outs[0], ref) < 4e-3
-    assert torch.equal(outs[0], outs[1])                    # fixed summation order: bitwise reproducible
+    rd = None if r is None else r.to(DEV)
+    for plan, want in _conv_routes(cfg).items():            # the one-wave kernel's split-K plan, and the 8-wave tile's under plan 0
+        outs = []
+        for _ in range(2):
+            out = torch.empty(n * H * W, Co, dtype=torch.bfloat16, device=DEV)
+            _under_plan(ops, plan, lambda: ops.gemm(rows, pw, out, conv=dict(IH=H, IW=W, OH=H, OW=W, stride=1, pad=1, ups=0), residual=rd))
+            assert _variant(ops) == want, (plan, want, _variant(ops))
+            outs.append(out)
+        assert rel_l2(outs[0], ref) < 4e-3
+        assert torch.equal(outs[0], outs[1])                # fixed summation order: bitwise reproducible
 
 
 def test_tconv3_splitk(ops):
-    B, T, HW, Cc = 2, 4, 576, 1280                          # M = 4608: 72 tiles, K = 3840 (60 K tiles) -> 3 splits
-    x = bf(rnd(B, Cc, T, HW, 1, seed=1)); w = rnd(Cc, Cc, 3, 1, 1, seed=2, scale=(3 * Cc) ** -0.5); b = rnd(Cc, seed=3)
-    ref = F.conv3d(x.float(), bf(w).float(), b, padding=(1, 0, 0))
-    pw = ops.PackedWeight.tconv3(w, b, DEV)
-    rows = x.permute(0, 2, 3, 4, 1).reshape(-1, Cc).contiguous().to(DEV)
-    out = torch.empty_like(rows)
-    ops.gemm(rows, pw, out, tconv=dict(T=T, HW=HW))
-    assert rel_l2(out, ref.permute(0, 2, 3, 4, 1).reshape(-1, Cc)) < 4e-3
+    # M = 4608: 72 tiles, K = 3840 (60 K tiles) -> 3 splits; on the one-wave kernel by default (K >= 1920)
+    _tconv3_routed(ops, 2, 4, 576, 1280, 0, {19: _PIPE + "<tconv>+splitk", 0: _G + "<320,tconv>+splitk"})
 
 
 # ---- persistent 256 x 320 kernel in conv / temporal-conv mode (>= 512 tiles, K <= 2880)
@@ -684,7 +741,7 @@ def test_tconv3_splitk(ops):
     dict(n=16, C=64, Co=320, H=192, W=192, stride=2, pad=0, ups=0),       # AE-style asymmetric pad
 ])
 def test_conv3x3_persistent(ops, cfg):
-    test_conv3x3(ops, cfg)
+    _conv3x3(ops, cfg, _conv_routes(cfg))
 
 
 def test_conv3x3_persistent_residual_rowvec(ops):
@@ -697,24 +754,19 @@ def test_conv3x3_persistent_residual_rowvec(ops):
     ref = bf(ref).float() + r.float()
     pw = ops.PackedWeight.conv3x3(w, b, DEV)
     rows = x.permute(0, 2, 3, 1).reshape(-1, C).contiguous().to(DEV)
-    out = torch.empty(n * H * W, Co, dtype=torch.bfloat16, device=DEV)
-    ops.gemm(rows, pw, out, conv=dict(IH=H, IW=W, OH=H, OW=W, stride=1, pad=1, ups=0), residual=r.to(DEV),
-             rowvec=emb.to(DEV), rows_per_vec=4 * H * W)
-    assert rel_l2(out, ref) < 4e-3
+    rd, embd = r.to(DEV), emb.to(DEV)
+    # 576 x 2 = 1152 tiles: the persistent conv kernel where the one-wave kernel is off (plan 0); the one-wave kernel by default
+    for plan, want in {19: _PIPE + "<conv>", 0: _P + "<320,conv>"}.items():
+        out = torch.empty(n * H * W, Co, dtype=torch.bfloat16, device=DEV)
+        _under_plan(ops, plan, lambda: ops.gemm(rows, pw, out, conv=dict(IH=H, IW=W, OH=H, OW=W, stride=1, pad=1, ups=0), residual=rd,
+                                                rowvec=embd, rows_per_vec=4 * H * W))
+        assert _variant(ops) == want, (plan, want, _variant(ops))
+        assert rel_l2(out, ref) < 4e-3
 
 
 @pytest.mark.parametrize("B,T,HW", [(2, 16, 4608), (3, 5, 9830)])
 def test_tconv3_persistent(ops, B, T, HW):
-    Cc = 320
-    x = bf(rnd(B, Cc, T, HW, 1, seed=1)); w = rnd(Cc, Cc, 3, 1, 1, seed=2, scale=(3 * Cc) ** -0.5); b = rnd(Cc, seed=3)
-    ref = F.conv3d(x.float(), bf(w).float(), b, padding=(1, 0, 0))
-    pw = ops.PackedWeight.tconv3(w, b, DEV)
-    rows = x.permute(0, 2, 3, 4, 1).reshape(-1, Cc).contiguous().to(DEV)
-    r = bf(rnd(rows.shape[0], Cc, seed=4))
-    out = torch.empty_like(rows)
-    ops.gemm(rows, pw, out, tconv=dict(T=T, HW=HW), residual=r.to(DEV))
-    want = bf(ref.permute(0, 2, 3, 4, 1).reshape(-1, Cc)).float() + r.float()
-    assert rel_l2(out, want) < 4e-3
+    _tconv3_routed(ops, B, T, HW, 320, 4, {19: _P + "<320,tconv>"})
 
 
 # ---- the one-wave-per-SIMD 320-wide kernel (gemm_pipe16.h) behind dc_gemm_set_plan: same shapes, same checkers (plan 1: convs
@@ -820,7 +872,7 @@ def test_conv3x3_upsample_fused_pipe16(ops, gemm_plan, cfg):
 @pytest.mark.parametrize("gemm_plan", [3], indirect=True)
 def test_gemm_and_tconv_pipe_plan(ops, gemm_plan):
     # plain rows (K = 2560, split-K plan of 72 tiles) and the temporal 3-tap mode of the same kernel
-    test_gemm_plain_large(ops, 4608 + 33, 1280, 2560)
+    _gemm_plain_large(ops, 4608 + 33, 1280, 2560)
     assert "gemm_pipe320" in _variant(ops) or "gemm_persist" in _variant(ops) or "glds" in _variant(ops)
     M, N, K = 18432, 1280, 5120
     x = bf(rnd(M, K, seed=1)); w = rnd(N, K, seed=2, scale=K ** -0.5); b = rnd(N, seed=3)
@@ -829,9 +881,9 @@ def test_gemm_and_tconv_pipe_plan(ops, gemm_plan):
     ops.gemm(x.to(DEV), pw, out)
     assert "gemm_pipe320" in _variant(ops), _variant(ops)
     assert rel_l2(out, x.float() @ bf(w).float().t() + b) < 4e-3
-    test_tconv3_splitk(ops)
+    _tconv3_routed(ops, 2, 4, 576, 1280, 0, None)
     assert "gemm_pipe320" in _variant(ops), _variant(ops)
-    test_tconv3_ragged_wide(ops)
+    _tconv3_routed(ops, 2, 16, 577, 640, 0, None, twice=True)
 
 
 # ---- conv_in as im2col (9 taps x 8 channels -> one 128-wide K) + plain GEMM, against torch and against the implicit-GEMM conv
