@@ -44,6 +44,16 @@ class DcDdimParams(C.Structure):
     ]
 
 
+class DcInvertParams(C.Structure):
+    _fields_ = [
+        ("sqrt_a_src", C.c_void_p), ("sqrt_1ma_src", C.c_void_p), ("sqrt_a_dst", C.c_void_p),
+        ("sqrt_1ma_dst", C.c_void_p), ("scale_ratio", C.c_void_p), ("step_index", C.c_void_p),
+        ("index", C.c_int), ("v_param", C.c_int),
+        ("cfg_scale", C.c_float), ("cfg_img", C.c_float), ("guidance_rescale", C.c_float),
+        ("e_nchw", C.c_int),
+    ]
+
+
 class DcDpmParams(C.Structure):
     _fields_ = [
         ("A", C.c_void_p), ("alpha_t", C.c_void_p), ("alpha_p_r", C.c_void_p), ("k", C.c_void_p), ("N", C.c_void_p),
@@ -104,6 +114,7 @@ SIGNATURES = {
     "dc_add_rows": (_I, [_P, _I, _P, _I, _P, _I, _I, _I, _P]),
     "dc_vae_sample": (_I, [_P, _I, _P, _P, _I, _I, _I, _F, _P]),
     "dc_ddim_step": (_I, [C.POINTER(DcDdimParams), _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
+    "dc_ddim_invert_step": (_I, [C.POINTER(DcInvertParams), _P, _P, _P, _I, _P, _P, _P, _I, _I, _I, _P, _P]),
     "dc_dpmpp_step": (_I, [C.POINTER(DcDpmParams), _P, _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P]),
     "dc_sds_noise": (_I, [C.POINTER(DcSdsParams), _P, _P, _P, _I, _L, _P]),
     "dc_sds_step": (_I, [C.POINTER(DcSdsParams), _P, _P, _I, _P, _P, _P, _P, _I, _I, _I, _P, _P]),

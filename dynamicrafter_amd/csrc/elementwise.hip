@@ -463,6 +463,45 @@ __global__ __launch_bounds__(256) void ddim_apply_kernel(const DcDdimParams p, c
 }
 
 // ---------------------------------------------------------------------------------------------------------
+// DDIM inversion: the deterministic step from level a_prev[k] up to a_t[k] (include/dcrafter_hip.h states the formula).
+// The model output is formed exactly as ddim_apply_kernel forms it (ddim_cfg, rescale_factor on ddim_partial_kernel's
+// partials); the conversion to eps / x0 uses the SOURCE level's coefficients, the re-noising the destination's.
+// Per element: e_c [, e_u, e_i], x in; x_next, pred_x0 out. No noise.
+__global__ __launch_bounds__(256) void ddim_invert_apply_kernel(const DcInvertParams p, const float* __restrict__ ec,
+                                                                const float* __restrict__ eu,
+                                                                const float* __restrict__ ei, int ld_e,
+                                                                const float* x,       // x and x_next may alias (in place)
+                                                                float* x_next, float* __restrict__ pred_x0, int C,
+                                                                int THW, const float* __restrict__ ws) {
+    __shared__ double tot[4];
+    const int b = blockIdx.y;
+    const int64_t n = (int64_t)C * THW;
+    const CfgArgs q = cfg_args(p);
+    const float factor = rescale_factor(p.guidance_rescale, eu, ws, b, n, tot);
+    const int idx = step_idx(p);
+    const float sq_src = p.sqrt_a_src[idx], sq_1m_src = p.sqrt_1ma_src[idx];
+    const float sq_dst = p.sqrt_a_dst[idx], sq_1m_dst = p.sqrt_1ma_dst[idx];
+    const float resc = p.scale_ratio ? p.scale_ratio[idx] : 1.0f;
+    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (int64_t)gridDim.x * 256) {
+        const int c = (int)(i / THW), pos = (int)(i - (int64_t)c * THW);     // NCTHW order for x / outputs
+        const size_t eoff = ddim_eoff(q, b, c, pos, C, THW, ld_e);
+        const size_t xoff = (size_t)b * n + i;
+        const float mo = ddim_cfg(q, ec, eu, ei, eoff) * factor;
+        const float xv = x[xoff];
+        float e_t, px0;
+        if (p.v_param) {
+            e_t = sq_src * mo + sq_1m_src * xv;
+            px0 = sq_src * xv - sq_1m_src * mo;
+        } else {
+            e_t = mo;
+            px0 = (xv - sq_1m_src * e_t) / sq_src;   // a_prev[k] > 0 for every k: no division by zero
+        }
+        x_next[xoff] = sq_dst * (px0 / resc) + sq_1m_dst * e_t;   // undoes the forward step's pred_x0 *= scale_ratio
+        pred_x0[xoff] = px0;
+    }
+}
+
+// ---------------------------------------------------------------------------------------------------------
 // DPM-Solver++ 2M / 2M SDE update (data-prediction multistep form). The guidance-rescale statistics come from
 // ddim_partial_kernel (same workspace layout, same fixed reduction order); this one pass converts the model output to
 // the raw x0_i, forms D = (1 + k) x0_i - k x0_{i-1} with x0_{i-1} from the history ring, and writes x_prev,
@@ -886,6 +925,29 @@ extern "C" int dc_ddim_step(const DcDdimParams* pp, const float* e_cond, const f
     const int64_t n = (int64_t)C * THW;
     hipLaunchKernelGGL(ddim_apply_kernel, dim3(grid_for(n, 256, 1024), B), dim3(256), 0, stream, p, e_cond, e_uncond,
                        e_img, ld_e, x, noise, x_prev, pred_x0, C, THW, workspace);
+    DC_CHECK_LAUNCH();
+    return 0;
+}
+
+extern "C" int dc_ddim_invert_step(const DcInvertParams* pp, const float* e_cond, const float* e_uncond,
+                                   const float* e_img, int ld_e, const float* x, float* x_next, float* pred_x0, int B,
+                                   int C, int THW, float* workspace, void* stream_) {
+    if (!pp || !e_cond || !x || !x_next || !pred_x0 || !workspace) return DC_ERR_ARG;
+    const DcInvertParams& p = *pp;
+    if (!p.sqrt_a_src || !p.sqrt_1ma_src || !p.sqrt_a_dst || !p.sqrt_1ma_dst) return DC_ERR_ARG;
+    if (e_img && !e_uncond) return DC_ERR_ARG;
+    if (!p.step_index && p.index < 0) return DC_ERR_ARG;
+    if (B < 1 || C < 1 || THW < 1) return DC_ERR_SHAPE;
+    if (!p.e_nchw && ld_e < C) return DC_ERR_SHAPE;
+    hipStream_t stream = (hipStream_t)stream_;
+    if (p.guidance_rescale > 0.f && e_uncond) {
+        hipLaunchKernelGGL(ddim_partial_kernel, dim3(DDIM_BLOCKS, B), dim3(256), 0, stream, cfg_args(p), e_cond, e_uncond,
+                           e_img, ld_e, C, THW, workspace);
+        DC_CHECK_LAUNCH();
+    }
+    const int64_t n = (int64_t)C * THW;
+    hipLaunchKernelGGL(ddim_invert_apply_kernel, dim3(grid_for(n, 256, 1024), B), dim3(256), 0, stream, p, e_cond,
+                       e_uncond, e_img, ld_e, x, x_next, pred_x0, C, THW, workspace);
     DC_CHECK_LAUNCH();
     return 0;
 }

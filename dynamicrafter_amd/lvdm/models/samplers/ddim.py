@@ -17,6 +17,9 @@ behaves as the reference's, including the 3-branch guidance of ddim_multiplecond
   * `window_stride=` (not in the reference) samples clips longer than the UNet's `temporal_length` by temporal
     co-denoising: `shape`'s frame count is then T_long, the UNet runs on overlapping windows of the long latent and their
     outputs are blended ahead of the unchanged update (samplers/windows.py, WindowedRun below).
+  * `encode` (not in the reference, which leaves it as a TODO at :179) is DDIM inversion: InvertRun below, one
+    dc_ddim_invert_step per step. `decode` and `ddim_sampling(timesteps=k)` run the last n steps of the schedule on the
+    same fused path as `sample` (a FusedRun over the tail of the execution-order tables), DESIGN 4.11.
 """
 import numpy as np
 import torch
@@ -136,10 +139,20 @@ class FusedRun(StepRun):
 
     def __init__(self, sampler, img, branches, *, fs=None, noises=None, cfg_scale=1.0, cfg_img=None,
                  guidance_rescale=0.0, temperature=1.0, mask=None, x0=None, q_noises=None, clean_cond=False,
-                 windows=None):
-        t_host = torch.as_tensor(sampler._exec_timesteps.copy(), dtype=torch.int64)
+                 windows=None, last=None):
+        # `last`: a partial run over the last n steps of the schedule (decode, timesteps=): the execution-order tables and
+        # the timestep table are sliced, so the counter still starts at 0 and noises / q_noises are [n, ...]
+        S_all = int(sampler._exec_timesteps.shape[0])
+        n = S_all if last is None else int(last)
+        if not 1 <= n <= S_all:
+            raise ValueError(f"a partial run covers 1 .. {S_all} steps, got {n}")
+        if n < S_all and windows is not None:
+            raise ValueError("partial runs are not implemented with windows")
+        t_host = torch.as_tensor(sampler._exec_timesteps[S_all - n:].copy(), dtype=torch.int64)
         super().__init__(sampler.model, img, branches, t_host[:, None].expand(-1, img.shape[0]), fs=fs, windows=windows)
         self.sampler = sampler
+        self.tables = sampler._tables if n == S_all else \
+            {k: v[S_all - n:] for k, v in sampler._tables.items() if not k.startswith("inv_")}
         self.noises, self.blend = _step_inputs(img, self.S, noises, mask, x0, q_noises, clean_cond,
                                                long_branches=None if windows is None else branches)
         self.pred_x0 = torch.empty_like(img)
@@ -149,7 +162,7 @@ class FusedRun(StepRun):
     def _enqueue(self):
         if self.blend is not None:
             b = self.blend
-            ops.mask_blend(self.img, b["x0"], b["mask"], b["q"], self.sampler._tables, step_index=self.counter,
+            ops.mask_blend(self.img, b["x0"], b["mask"], b["q"], self.tables, step_index=self.counter,
                            clean=b["clean"], noise_step_stride=self.img.numel())
         e = self._evaluate()
         M = self.kw["B"] * self.kw["THW"]
@@ -163,8 +176,44 @@ class FusedRun(StepRun):
         return self.model.apply_model_rows(self.img, self.prep, self.t_table, t_index=self.counter)
 
     def _update(self, e_c, e_u, e_i):
-        ops.ddim_step(self.sampler._tables, e_c, e_u, e_i, self.img, self.noises, self.img, self.pred_x0, self.ws,
+        ops.ddim_step(self.tables, e_c, e_u, e_i, self.img, self.noises, self.img, self.pred_x0, self.ws,
                       step_index=self.counter, **self.kw)
+
+
+_INVERT_TABLES = ("inv_sqrt_a_src", "inv_sqrt_1ma_src", "inv_sqrt_a_dst", "inv_sqrt_1ma_dst", "inv_scale_ratio")
+
+
+def _invert_kw(m, x, cfg_scale, cfg_img, guidance_rescale, **extra):
+    kw = _update_kw(m, x, cfg_scale, cfg_img, guidance_rescale, 1.0, **extra)
+    del kw["temperature"]                               # an inversion draws no noise
+    return kw
+
+
+class InvertRun(StepRun):
+    """One fused DDIM inversion run over the DDIM indices k = 0 .. n - 1, in that order: per step the batched UNet on the
+    latent at the source level's own timestep (`sampler._inv_timesteps`) + dc_ddim_invert_step, which leaves the latent
+    of the next level in `img` and the step's `pred_x0`. The tables are in ascending k already, so the counter indexes
+    them as they are."""
+
+    def __init__(self, sampler, img, branches, n, *, fs=None, cfg_scale=1.0, cfg_img=None, guidance_rescale=0.0):
+        S_all = int(sampler._inv_timesteps.shape[0])
+        if not 1 <= int(n) <= S_all:
+            raise ValueError(f"an inversion covers 1 .. {S_all} steps, got {n}")
+        t_host = torch.as_tensor(sampler._inv_timesteps[:int(n)].copy(), dtype=torch.int64)
+        super().__init__(sampler.model, img, branches, t_host[:, None].expand(-1, img.shape[0]), fs=fs)
+        self.sampler = sampler
+        self.tables = {k: sampler._tables[k][:int(n)] for k in _INVERT_TABLES if k in sampler._tables}
+        self.pred_x0 = torch.empty_like(img)
+        self.kw = _invert_kw(self.model, img, cfg_scale, cfg_img, guidance_rescale)
+
+    def _enqueue(self):
+        e = self.model.apply_model_rows(self.img, self.prep, self.t_table, t_index=self.counter)
+        M = self.kw["B"] * self.kw["THW"]
+        e_u = e[M:2 * M] if self.nb > 1 else None
+        e_i = e[2 * M:3 * M] if self.nb > 2 else None
+        ops.ddim_invert_step(self.tables, e[:M], e_u, e_i, self.img, self.img, self.pred_x0, self.ws,
+                             step_index=self.counter, **self.kw)
+        ops.advance_counter(self.counter)
 
 
 class WindowedRun:
@@ -285,6 +334,18 @@ class DDIMSampler(object):
              "sqrt_1macp_t": m.sqrt_one_minus_alphas_cumprod.detach().float().cpu()[ts][order].contiguous().to(dev)}
         if getattr(m, "use_dynamic_rescale", False):
             t["scale_ratio"] = (self.ddim_scale_arr_prev / self.ddim_scale_arr)[order].contiguous().to(dev)
+        # inversion (encode): step k takes the latent from level a_prev[k] up to a[k] after a UNet call at the source level's
+        # own timestep t_src[k] (0 for k = 0, else ddim_timesteps[k - 1], so a_prev[k] = alphas_cumprod[t_src[k]]). Tables in
+        # ASCENDING k, which is an inversion's execution order; float64 on the host, cast once
+        self._inv_timesteps = np.concatenate([[0], self.ddim_timesteps[:-1]]).astype(np.int64)
+        src = torch.as_tensor(self._inv_timesteps)
+        up = lambda v: torch.as_tensor(np.asarray(v, dtype=np.float64)).float().contiguous().to(dev)
+        a64 = a.double().numpy()
+        t.update(inv_sqrt_a_src=m.sqrt_alphas_cumprod.detach().float().cpu()[src].contiguous().to(dev),
+                 inv_sqrt_1ma_src=m.sqrt_one_minus_alphas_cumprod.detach().float().cpu()[src].contiguous().to(dev),
+                 inv_sqrt_a_dst=up(np.sqrt(a64)), inv_sqrt_1ma_dst=up(np.sqrt(1.0 - a64)))
+        if getattr(m, "use_dynamic_rescale", False):
+            t["inv_scale_ratio"] = up((self.ddim_scale_arr_prev.double() / self.ddim_scale_arr.double()).numpy())
         self._tables = t
         self._exec_timesteps = np.flip(self.ddim_timesteps).copy()
 
@@ -346,16 +407,43 @@ class DDIMSampler(object):
                       unconditional_conditioning=None, verbose=True, precision=None, fs=None, guidance_rescale=0.0,
                       noises=None, use_graph=False, window_stride=None, window_weights="triangle", window_shift=0,
                       windows_per_call=None, **kwargs):
-        if ddim_use_original_steps or timesteps is not None or quantize_denoised or score_corrector is not None \
-                or noise_dropout > 0.:
+        if ddim_use_original_steps or quantize_denoised or score_corrector is not None or noise_dropout > 0.:
             raise NotImplementedError("only the options DynamiCrafter inference uses are implemented "
-                                      "(no original-steps / partial / quantised / corrected sampling)")
+                                      "(no original-steps / quantised / corrected sampling)")
+        n = self._exec_timesteps.shape[0] if timesteps is None else self.subset_steps(timesteps)
+        return self._denoise(n, cond, shape, x_T=x_T, callback=callback, mask=mask, x0=x0, img_callback=img_callback,
+                             log_every_t=log_every_t, temperature=temperature,
+                             unconditional_guidance_scale=unconditional_guidance_scale,
+                             unconditional_conditioning=unconditional_conditioning, fs=fs,
+                             guidance_rescale=guidance_rescale, noises=noises, use_graph=use_graph,
+                             window_stride=window_stride, window_weights=window_weights, window_shift=window_shift,
+                             windows_per_call=windows_per_call, **kwargs)
+
+    def subset_steps(self, timesteps):
+        """How many steps `ddim_sampling(timesteps=k)` runs: the DDIM indices range(S)[:subset_end], descending, with the
+        reference's expression for subset_end taken literally (ddim.py:155-156) - its off-by-one, float rounding and
+        Python's slicing of a negative subset_end (k = 0 selects all but the last index) included."""
+        S = self.ddim_timesteps.shape[0]
+        subset_end = int(min(timesteps / S, 1) * S) - 1
+        return len(range(S)[:subset_end])
+
+    def _denoise(self, n, cond, shape, x_T=None, callback=None, mask=None, x0=None, img_callback=None, log_every_t=100,
+                 temperature=1., unconditional_guidance_scale=1., unconditional_conditioning=None, fs=None,
+                 guidance_rescale=0.0, noises=None, use_graph=False, window_stride=None, window_weights="triangle",
+                 window_shift=0, windows_per_call=None, **kwargs):
+        """The last `n` steps of the schedule from x_T (all S of them: ddim_sampling; fewer: timesteps= and decode).
+        Executed step i of the n is step S - n + i of the full run and indexes `noises` / `q_noises` ([n, ...]) by i."""
         m = self.model
         dev = m.device
         if dev.type != "cuda":
             raise RuntimeError(f"{type(self).__name__} runs on the HIP path only: put the model on the GPU")
         img = (torch.randn(shape, device=dev) if x_T is None else x_T.to(dev)).to(torch.float32).contiguous().clone()
-        S = self._exec_timesteps.shape[0]
+        S_all = self._exec_timesteps.shape[0]
+        if n == 0:                                       # an empty selection: the reference's loop body never runs
+            return img, {"x_inter": [img.clone()], "pred_x0": [img.clone()]}
+        if n < S_all and window_stride is not None:
+            raise ValueError("window_stride cannot be combined with a partial run (timesteps= / decode)")
+        S, off = n, S_all - n
         window = None
         if window_stride is not None:
             T = getattr(m, "temporal_length", None)
@@ -394,7 +482,8 @@ class DDIMSampler(object):
             cls, wkw = (self._run_class, {}) if window is None else (windowed(self._run_class), dict(window=window))
             run = cls(self, img, branches, fs=fs, noises=noises, cfg_scale=unconditional_guidance_scale,
                       cfg_img=kwargs.get("cfg_img"), guidance_rescale=guidance_rescale, temperature=temperature,
-                      mask=mask, x0=x0, q_noises=q_noises, clean_cond=clean_cond, **wkw)
+                      mask=mask, x0=x0, q_noises=q_noises, clean_cond=clean_cond, **wkw,
+                      **({} if off == 0 else {"last": n}))
             if use_graph:
                 run.capture()
         else:
@@ -414,12 +503,12 @@ class DDIMSampler(object):
             else:
                 if blend is not None:
                     img = ops.mask_blend(img.contiguous().clone(), blend["x0"], blend["mask"],
-                                         None if blend["clean"] else blend["q"][i], self._tables, index=i,
+                                         None if blend["clean"] else blend["q"][i], self._tables, index=off + i,
                                          clean=blend["clean"])
                 if proxy is not None:
                     proxy.step = i
-                img, pred_x0 = update(img, i, None if noises is None else noises[i])
-            index = S - i - 1
+                img, pred_x0 = update(img, off + i, None if noises is None else noises[i])
+            index = S - i - 1                  # total_steps - i - 1 with the reference's total_steps = n (ddim.py:160-170)
             log_now = index % log_every_t == 0 or index == S - 1
             if run is not None and use_graph and (callback or img_callback or log_now):
                 run.sync()                     # the graph runs on its own stream: the step must have finished before the
@@ -479,18 +568,86 @@ class DDIMSampler(object):
 
     @torch.no_grad()
     def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
-               use_original_steps=False, callback=None):
-        """ddim.py:281-301: run the last t_start DDIM steps from x_latent."""
+               use_original_steps=False, callback=None, *, fs=None, guidance_rescale=0.0, cfg_img=None,
+               unconditional_conditioning_img_nonetext=None, noises=None, temperature=1., mask=None, x0=None,
+               q_noises=None, use_graph=False, img_callback=None, log_every_t=100):
+        """ddim.py:281-301: run the last t_start DDIM steps from x_latent (at level ddim_alphas[t_start - 1]) and return
+        the result. The steps are those of `sample`, on the same path (a partial FusedRun when the model has the batched
+        entry), so the keyword-only options mean what they mean there; `noises` / `q_noises` are [t_start, ...], indexed
+        by the executed step. Without `fs` none is passed to the model, as in the reference."""
         if use_original_steps:
             raise NotImplementedError
-        S = self.ddim_timesteps.shape[0]
-        steps = np.flip(self.ddim_timesteps[:t_start])
-        x_dec = x_latent
-        for i, step in enumerate(steps):
-            index = steps.shape[0] - i - 1
-            ts = torch.full((x_latent.shape[0],), int(step), device=x_latent.device, dtype=torch.long)
-            x_dec, _ = self.p_sample_ddim(x_dec, cond, ts, index=index,
-                                          unconditional_guidance_scale=unconditional_guidance_scale,
-                                          unconditional_conditioning=unconditional_conditioning)
-            if callback: callback(i)
+        n = len(self.ddim_timesteps[:t_start])
+        kw = {}
+        if cfg_img is not None:
+            kw["cfg_img"] = cfg_img
+        if unconditional_conditioning_img_nonetext is not None:
+            kw["unconditional_conditioning_img_nonetext"] = unconditional_conditioning_img_nonetext
+        if q_noises is not None:
+            kw["q_noises"] = q_noises
+        x_dec, _ = self._denoise(n, cond, tuple(x_latent.shape), x_T=x_latent, callback=callback, mask=mask, x0=x0,
+                                 img_callback=img_callback, log_every_t=log_every_t, temperature=temperature,
+                                 unconditional_guidance_scale=unconditional_guidance_scale,
+                                 unconditional_conditioning=unconditional_conditioning, fs=fs,
+                                 guidance_rescale=guidance_rescale, noises=noises, use_graph=use_graph, **kw)
         return x_dec
+
+    @torch.no_grad()
+    def encode(self, x0, c, t_enc, use_original_steps=False, return_intermediates=None,
+               unconditional_guidance_scale=1.0, unconditional_conditioning=None, callback=None, *, fs=None,
+               guidance_rescale=0.0, use_graph=False, **kwargs):
+        """DDIM inversion: the deterministic pass from the clean latent x0 up to level ddim_alphas[t_enc - 1], where
+        `decode(x, c, t_enc)` starts - the reference's TODO at ddim.py:179, with the signature of the latent-diffusion
+        sampler's `encode`. Runs the inverse steps k = 0 .. t_enc - 1 (include/dcrafter_hip.h: dc_ddim_invert_step; the
+        UNet sees the latent at the source level's timestep): InvertRun when the model has the batched entry and the
+        conditionings are dicts, else separate apply_model calls and the same kernel. Three-branch guidance through
+        `cfg_img` / `unconditional_conditioning_img_nonetext`. Returns (x_encoded, {"x_inter": [...], "pred_x0": [...]}):
+        with return_intermediates = r the latent and pred_x0 after every max(t_enc // r, 1)-th step and after the last."""
+        if use_original_steps:
+            raise NotImplementedError("encode runs on the DDIM timesteps only")
+        if kwargs.get("window_stride") is not None:
+            raise ValueError("encode: windowed (long-clip) inversion is not defined")
+        S = self.ddim_timesteps.shape[0]
+        if not isinstance(t_enc, (int, np.integer)) or not 1 <= t_enc <= S:
+            raise ValueError(f"encode: t_enc must be an integer in 1 .. {S}, got {t_enc!r}")
+        n = int(t_enc)
+        m = self.model
+        dev = m.device
+        if dev.type != "cuda":
+            raise RuntimeError(f"{type(self).__name__} runs on the HIP path only: put the model on the GPU")
+        img = x0.to(dev).to(torch.float32).contiguous().clone()
+        branches = self._branches(c, unconditional_conditioning, unconditional_guidance_scale, kwargs)
+        cfg_img = kwargs.get("cfg_img")
+        inter = {"x_inter": [], "pred_x0": []}
+        every = max(n // int(return_intermediates), 1) if return_intermediates else 0
+        run = None
+        if hasattr(m, "apply_model_rows") and all(isinstance(b, dict) for b in branches):
+            run = InvertRun(self, img, branches, n, fs=fs, cfg_scale=unconditional_guidance_scale, cfg_img=cfg_img,
+                            guidance_rescale=guidance_rescale)
+            if use_graph:
+                run.capture()
+        else:
+            ws = ops.step_workspace(img.shape[0], dev)
+            kw = _invert_kw(m, img, unconditional_guidance_scale, cfg_img, guidance_rescale, e_nchw=True)
+            mk = {} if fs is None else {"fs": fs}
+        for k in range(n):
+            if run is not None:
+                run.step()
+                pred_x0 = run.pred_x0
+            else:
+                ts = torch.full((img.shape[0],), int(self._inv_timesteps[k]), device=dev, dtype=torch.long)
+                e = [m.apply_model(img, ts, b, **mk).to(torch.float32).contiguous() for b in branches]
+                e += [None] * (3 - len(e))
+                img, pred_x0 = ops.ddim_invert_step(self._tables, e[0], e[1], e[2], img, torch.empty_like(img),
+                                                    torch.empty_like(img), ws, index=k, **kw)
+            log_now = every and (k % every == 0 or k == n - 1)
+            if run is not None and use_graph and (callback or log_now):
+                run.sync()
+            if callback: callback(k)
+            if log_now:
+                inter["x_inter"].append(img.clone())
+                inter["pred_x0"].append(pred_x0.clone())
+        if run is not None:
+            run.sync()
+            self._last_run = run
+        return img, inter

@@ -133,3 +133,12 @@ class DPMSolverSampler(DDIMSampler):
 
     def decode(self, *args, **kwargs):
         raise NotImplementedError("decode runs DDIM steps from a latent; use DDIMSampler for it")
+
+    def encode(self, *args, **kwargs):
+        raise NotImplementedError("encode is DDIM inversion; a multistep solver needs its own: use DDIMSampler for it")
+
+    def ddim_sampling(self, cond, shape, *args, **kwargs):
+        # a multistep solver started inside the schedule needs a restart rule of its own (its x0 history is empty there)
+        if kwargs.get("timesteps") is not None or (len(args) > 3 and args[3] is not None):
+            raise NotImplementedError("timesteps= (a partial run) is implemented for DDIMSampler only")
+        return super().ddim_sampling(cond, shape, *args, **kwargs)

@@ -806,6 +806,49 @@ def ddim_step(tables, e_cond, e_uncond, e_img, x, noise, x_prev, pred_x0, worksp
     return x_prev, pred_x0
 
 
+_INVERT_FIELDS = {"sqrt_a_src": "inv_sqrt_a_src", "sqrt_1ma_src": "inv_sqrt_1ma_src", "sqrt_a_dst": "inv_sqrt_a_dst",
+                  "sqrt_1ma_dst": "inv_sqrt_1ma_dst", "scale_ratio": "inv_scale_ratio"}
+
+
+def ddim_invert_step(tables, e_cond, e_uncond, e_img, x, x_next, pred_x0, workspace, *, B, Cc, THW, index=0,
+                     step_index=None, v_param=False, cfg_scale=1.0, cfg_img=1.0, guidance_rescale=0.0, e_nchw=False,
+                     ld_e=None):
+    """One DDIM inversion step (dc_ddim_invert_step): x at level ddim_alphas_prev[k] -> x_next at ddim_alphas[k], k the
+    step. tables: dict of fp32 device vectors in ascending k - inv_sqrt_a_src, inv_sqrt_1ma_src, inv_sqrt_a_dst,
+    inv_sqrt_1ma_dst [, inv_scale_ratio] (DDIMSampler.make_schedule). x and x_next may be the same tensor."""
+    p = _hip.DcInvertParams()
+    steps = None
+    for f, k in _INVERT_FIELDS.items():
+        t = tables.get(k)
+        if t is None:
+            if f != "scale_ratio":
+                raise ValueError(f"ddim_invert_step: table {k} is missing")
+        else:
+            if t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"ddim_invert_step: table {k} must be contiguous fp32")
+            if steps is not None and t.numel() != steps:
+                raise ValueError(f"ddim_invert_step: table {k} has {t.numel()} entries, the others {steps}")
+            steps = t.numel()
+        setattr(p, f, 0 if t is None else t.data_ptr())
+    if step_index is None and not 0 <= index < steps:
+        raise ValueError(f"ddim_invert_step: step {index} is outside the tables' {steps} steps")
+    if e_img is not None and e_uncond is None:
+        raise ValueError("ddim_invert_step: e_img needs e_uncond")
+    if ld_e is None:
+        ld_e = 0 if e_nchw else e_cond.stride(0)
+    if not e_nchw and ld_e < Cc:
+        raise ValueError(f"ddim_invert_step: ld_e = {ld_e} is below the {Cc} channels")
+    p.step_index = 0 if step_index is None else step_index.data_ptr()
+    p.index, p.v_param, p.e_nchw = index, 1 if v_param else 0, 1 if e_nchw else 0
+    p.cfg_scale, p.cfg_img, p.guidance_rescale = cfg_scale, cfg_img, guidance_rescale
+    _need_step(((x, "x"), (x_next, "x_next"), (pred_x0, "pred_x0")), workspace,
+               ((e_cond, "e_cond"), (e_uncond, "e_uncond"), (e_img, "e_img")), B=B, Cc=Cc, THW=THW, e_nchw=e_nchw, ld_e=ld_e)
+    check(_hip.lib().dc_ddim_invert_step(C.byref(p), _ptr(e_cond), _ptr(e_uncond), _ptr(e_img), ld_e, _ptr(x),
+                                         _ptr(x_next), _ptr(pred_x0), B, Cc, THW, _ptr(workspace), stream_ptr()),
+          "dc_ddim_invert_step")
+    return x_next, pred_x0
+
+
 def dpmpp_step(tables, e_cond, e_uncond, e_img, x, noise, x_prev, pred_x0, workspace, x0_hist, *, B, Cc, THW, index=0,
                step_index=None, v_param=False, cfg_scale=1.0, cfg_img=1.0, guidance_rescale=0.0, temperature=1.0,
                e_nchw=False, ld_e=None, noise_step_stride=0):

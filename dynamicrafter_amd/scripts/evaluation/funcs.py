@@ -7,6 +7,7 @@ reference's `scripts/evaluation/funcs.py`, same names and signatures.
     load_image_batch         funcs.py:182-203   image files (or the first frame of an .avi) -> [n, 3, h, w] in [-1, 1] on the device
     load_video_batch         funcs.py:143-179   Motion-JPEG .avi clips -> [b, 3, t, h, w] in [-1, 1] on the device (HIP JPEG decoder)
     save_videos              funcs.py:206-218   [b, n_samples, c, t, h, w] -> one clip file per batch entry
+    video_guided_synthesis   (not in the reference) re-exported from edit.py: a load_video_batch clip + an edited first frame -> clip
 
 `get_filelist(data_dir, ext="*")` here is the reference's funcs.py signature; inference.py keeps its own
 `get_filelist(data_dir, postfixes)`, as the reference does.
@@ -20,6 +21,7 @@ import torch
 from ...lvdm.models.samplers.ddim import DDIMSampler
 from ...lvdm.models.samplers.dpm_solver import SOLVERS as DPM_SOLVERS
 from ...lvdm.models.samplers.dpm_solver import DPMSolverSampler
+from .edit import video_guided_synthesis  # noqa: F401  (re-exported)
 from .inference import get_latent_z, load_model_checkpoint, load_prompts  # noqa: F401  (re-exported)
 
 

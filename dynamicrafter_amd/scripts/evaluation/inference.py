@@ -2,6 +2,7 @@
 sit between the data loader and the sampler.
 
     image_guided_synthesis   inference.py:216-313   conditioning assembly -> DDIM (or DPM-Solver++) loop -> decode
+    build_conditioning       inference.py:232-273   the conditioning assembly of image_guided_synthesis, shared with edit.py
     get_latent_z             inference.py:164-169   video -> per-frame AE latents
     load_model_checkpoint    inference.py:34-59     Lightning / DeepSpeed state dict -> model (key renames kept)
     get_filelist             funcs.py / inference.py:26-32   sorted glob by suffix
@@ -69,6 +70,51 @@ def get_latent_z(model, videos):
     return z.reshape(b, t, *z.shape[1:]).permute(0, 2, 1, 3, 4).contiguous()
 
 
+def build_conditioning(model, prompts, videos, unconditional_guidance_scale=1.0, cfg_img=None, multiple_cond_cfg=False,
+                       ends_only=False, num_frames=None):
+    """The conditioning assembly of inference.py:232-273, shared by image_guided_synthesis and video_guided_synthesis
+    (scripts/evaluation/edit.py): `videos` [b, 3, t, h, w] whose first frame is the guiding image -> (cond, uc, uc_2).
+    cond: text + image tokens in c_crossattn and, for a hybrid model, the image latent over all frames in c_concat
+    (`ends_only`: first and last frame only, zeros between, for loop / interp; `num_frames`: repeat over that many frames).
+    uc: the unconditional branch (None at guidance scale 1); uc_2: image yes, text "" (None unless multiple_cond_cfg and
+    cfg_img != 1)."""
+    batch_size = videos.shape[0]
+    img = videos[:, :, 0]                                         # b c h w
+    img_emb = model.image_proj_model(model.embedder(img))         # b (t l) c
+    cond_emb = model.get_learned_conditioning(prompts)
+    cond = {"c_crossattn": [torch.cat([cond_emb, img_emb], dim=1)]}
+    hybrid = model.model.conditioning_key == "hybrid"
+    if hybrid:
+        z = get_latent_z(model, videos)                           # b c t h w
+        if ends_only:
+            img_cat_cond = torch.zeros_like(z)
+            img_cat_cond[:, :, 0] = z[:, :, 0]
+            img_cat_cond[:, :, -1] = z[:, :, -1]
+        else:
+            img_cat_cond = z[:, :, :1].repeat(1, 1, z.shape[2] if num_frames is None else num_frames, 1, 1)
+        cond["c_concat"] = [img_cat_cond]
+
+    if unconditional_guidance_scale != 1.0:
+        if model.uncond_type == "empty_seq":
+            uc_emb = model.get_learned_conditioning(batch_size * [""])
+        elif model.uncond_type == "zero_embed":
+            uc_emb = torch.zeros_like(cond_emb)
+        uc_img_emb = model.image_proj_model(model.embedder(torch.zeros_like(img)))
+        uc = {"c_crossattn": [torch.cat([uc_emb, uc_img_emb], dim=1)]}
+        if hybrid:
+            uc["c_concat"] = [img_cat_cond]
+    else:
+        uc = None
+
+    # the third branch: image yes, text "" (inference.py:266-273)
+    uc_2 = None
+    if multiple_cond_cfg and cfg_img != 1.0:
+        uc_2 = {"c_crossattn": [torch.cat([uc_emb, img_emb], dim=1)]}
+        if hybrid:
+            uc_2["c_concat"] = [img_cat_cond]
+    return cond, uc, uc_2
+
+
 @torch.no_grad()
 def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddim_steps=50, ddim_eta=1.,
                            unconditional_guidance_scale=1.0, cfg_img=None, fs=None, text_input=False,
@@ -116,41 +162,9 @@ def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddi
     if not text_input:
         prompts = [""] * batch_size
 
-    img = videos[:, :, 0]                                         # b c h w
-    img_emb = model.image_proj_model(model.embedder(img))         # b (t l) c
-    cond_emb = model.get_learned_conditioning(prompts)
-    cond = {"c_crossattn": [torch.cat([cond_emb, img_emb], dim=1)]}
-    hybrid = model.model.conditioning_key == "hybrid"
-    if hybrid:
-        z = get_latent_z(model, videos)                           # b c t h w
-        if loop or interp:
-            img_cat_cond = torch.zeros_like(z)
-            img_cat_cond[:, :, 0] = z[:, :, 0]
-            img_cat_cond[:, :, -1] = z[:, :, -1]
-        else:
-            img_cat_cond = z[:, :, :1].repeat(1, 1, z.shape[2] if num_frames is None else num_frames, 1, 1)
-        cond["c_concat"] = [img_cat_cond]
-
-    if unconditional_guidance_scale != 1.0:
-        if model.uncond_type == "empty_seq":
-            uc_emb = model.get_learned_conditioning(batch_size * [""])
-        elif model.uncond_type == "zero_embed":
-            uc_emb = torch.zeros_like(cond_emb)
-        uc_img_emb = model.image_proj_model(model.embedder(torch.zeros_like(img)))
-        uc = {"c_crossattn": [torch.cat([uc_emb, uc_img_emb], dim=1)]}
-        if hybrid:
-            uc["c_concat"] = [img_cat_cond]
-    else:
-        uc = None
-
-    # the third branch: image yes, text "" (inference.py:266-273)
-    if multiple_cond_cfg and cfg_img != 1.0:
-        uc_2 = {"c_crossattn": [torch.cat([uc_emb, img_emb], dim=1)]}
-        if hybrid:
-            uc_2["c_concat"] = [img_cat_cond]
-        kwargs.update({"unconditional_conditioning_img_nonetext": uc_2})
-    else:
-        kwargs.update({"unconditional_conditioning_img_nonetext": None})
+    cond, uc, uc_2 = build_conditioning(model, prompts, videos, unconditional_guidance_scale, cfg_img, multiple_cond_cfg,
+                                        loop or interp, num_frames)
+    kwargs.update({"unconditional_conditioning_img_nonetext": uc_2})
 
     batch_variants = []
     for _ in range(n_samples):

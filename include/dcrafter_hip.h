@@ -233,6 +233,38 @@ int dc_ddim_step(const DcDdimParams* p, const float* e_cond, const float* e_unco
                  const float* x, const float* noise, float* x_prev, float* pred_x0, int B, int C, int THW,
                  float* workspace, void* stream);
 
+typedef struct DcInvertParams {
+    /* per-step fp32 tables in execution order, which for an inversion is ASCENDING DDIM index k; indexed by
+     * step_index[0] (device) when step_index != NULL, else by `index`. Host float64 -> fp32 (samplers/ddim.py). */
+    const float* sqrt_a_src;     /* sqrt(ap[k]): model.sqrt_alphas_cumprod[t_src[k]], t_src[0] = 0, else ddim_timesteps[k-1] */
+    const float* sqrt_1ma_src;   /* sqrt(1 - ap[k]): model.sqrt_one_minus_alphas_cumprod[t_src[k]] */
+    const float* sqrt_a_dst;     /* sqrt(ddim_alphas[k]) */
+    const float* sqrt_1ma_dst;   /* sqrt(1 - ddim_alphas[k]) */
+    const float* scale_ratio;    /* r[k] = ddim_scale_arr_prev[k]/ddim_scale_arr[k], or NULL (r = 1) */
+    const int32_t* step_index;   /* device counter or NULL */
+    int index;
+    int v_param;
+    float cfg_scale;
+    float cfg_img;
+    float guidance_rescale;
+    int e_nchw;                  /* as DcDdimParams */
+} DcInvertParams;
+
+/* One DDIM inversion step for B clips: the latent x at level ap[k] = ddim_alphas_prev[k] goes to level
+ * a[k] = ddim_alphas[k], the deterministic forward pass the reference leaves as a TODO
+ * ("# TODO: deterministic forward pass? <ddim inversion>", lvdm/models/samplers/ddim.py:179). The reference has no
+ * call site for it. With mo = CFG combine of e_cond [, e_uncond, e_img] followed by guidance rescale, formed exactly
+ * as dc_ddim_step forms it, the UNet having been evaluated on x at t_src[k]:
+ *   v:    eps = sqrt(ap) mo + sqrt(1 - ap) x,    x0s = sqrt(ap) x - sqrt(1 - ap) mo
+ *   eps:  eps = mo,                              x0s = (x - sqrt(1 - ap) eps) / sqrt(ap)
+ *   x_next = sqrt(a[k]) (x0s / r[k]) + sqrt(1 - a[k]) eps,    pred_x0 = x0s
+ * For equal eps this is the algebraic inverse of dc_ddim_step at eta = 0, the dynamic rescale included. ap[k] > 0 for
+ * every k; with zero-terminal SNR the last a[k] is 0 and x_next = eps. Operands as in dc_ddim_step without the noise
+ * (x and x_next may alias). workspace: >= 16 * B * 256 floats. */
+int dc_ddim_invert_step(const DcInvertParams* p, const float* e_cond, const float* e_uncond, const float* e_img,
+                        int ld_e, const float* x, float* x_next, float* pred_x0, int B, int C, int THW,
+                        float* workspace, void* stream);
+
 typedef struct DcDpmParams {
     /* per-step fp32 tables in execution order, indexed by step_index[0] (device) when step_index != NULL, else by
      * `index`. The solver's own tables (host float64 -> fp32, samplers/dpm_solver.py): */
