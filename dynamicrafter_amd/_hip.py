@@ -142,6 +142,10 @@ SIGNATURES = {
     "dc_resize_f32_h": (_I, [_P, _P, _P, _P, _P] + [_I] * 10 + [_P]),
     "dc_resize_f32_finish": (_I, [_P, _P, _P, _P, _P] + [_I] * 13 + [_P]),
     "dc_mask_blend": (_I, [_P, _P, _P, _P, _P, _P, _P, _I, _L, _L, _I, _P]),
+    "dc_freeu_scratch_floats": (_L, [_I] * 5),
+    "dc_freeu_skip_stats": (_I, [_P] + [_I] * 6 + [_P, _P, _P, _P]),
+    "dc_freeu_hmean": (_I, [_P] + [_I] * 6 + [_P, _P]),
+    "dc_freeu_apply": (_I, [_P] + [_I] * 6 + [_P, _F, _F, _P, _P, _P]),
     "dc_advance_counter": (_I, [_P, _P]),
     "dc_stream_create": (_I, [C.POINTER(_P)]),
     "dc_stream_destroy": (_I, [_P]),

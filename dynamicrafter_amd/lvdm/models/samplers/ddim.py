@@ -20,7 +20,13 @@ behaves as the reference's, including the 3-branch guidance of ddim_multiplecond
   * `encode` (not in the reference, which leaves it as a TODO at :179) is DDIM inversion: InvertRun below, one
     dc_ddim_invert_step per step. `decode` and `ddim_sampling(timesteps=k)` run the last n steps of the schedule on the
     same fused path as `sample` (a FusedRun over the tail of the execution-order tables), DESIGN 4.11.
+  * `freeu=dict(s1=, s2=, b1=, b2=, version=)` (not in the reference) on `sample`, `ddim_sampling`, `decode` and `encode`
+    runs that call with FreeU on the UNet (UNetModel.enable_freeu) and puts the model's previous setting
+    back afterwards, also when the call raises; None (default) leaves the model's setting as it is.
 """
+import contextlib
+import functools
+
 import numpy as np
 import torch
 
@@ -56,6 +62,33 @@ def _step_inputs(img, S, noises, mask, x0, q_noises, clean_cond, long_branches=N
             raise ValueError(f"{name}: the step kernels read step index * {img.numel()} + i for {S} steps; "
                              f"got {t.numel()} elements")
     return noises, blend
+
+
+@contextlib.contextmanager
+def freeu_scope(model, freeu):
+    """Run a block with `freeu` (enable_freeu's arguments as a dict) on the UNet of `model` (a LatentDiffusion: its
+    model.diffusion_model, or a UNetModel itself) and restore the setting that was in force before, whatever happens
+    inside. None changes nothing. A run captured inside the block keeps FreeU in its graph after the block ends."""
+    if freeu is None:
+        yield
+        return
+    net = getattr(getattr(model, "model", None), "diffusion_model", model)
+    if not hasattr(net, "set_freeu"):
+        raise ValueError(f"freeu=: {type(net).__name__} has no FreeU (expected the HIP UNetModel)")
+    prev = net.set_freeu(dict(freeu))          # validates before anything runs
+    try:
+        yield
+    finally:
+        net.set_freeu(prev)
+
+
+def _takes_freeu(fn):
+    """Gives a sampler method the keyword `freeu=` (freeu_scope around the whole call)."""
+    @functools.wraps(fn)
+    def wrapped(self, *args, freeu=None, **kwargs):
+        with freeu_scope(self.model, freeu):
+            return fn(self, *args, **kwargs)
+    return wrapped
 
 
 def _update_kw(m, x, cfg_scale, cfg_img, guidance_rescale, temperature, **extra):
@@ -427,6 +460,7 @@ class DDIMSampler(object):
         subset_end = int(min(timesteps / S, 1) * S) - 1
         return len(range(S)[:subset_end])
 
+    @_takes_freeu
     def _denoise(self, n, cond, shape, x_T=None, callback=None, mask=None, x0=None, img_callback=None, log_every_t=100,
                  temperature=1., unconditional_guidance_scale=1., unconditional_conditioning=None, fs=None,
                  guidance_rescale=0.0, noises=None, use_graph=False, window_stride=None, window_weights="triangle",
@@ -570,7 +604,7 @@ class DDIMSampler(object):
     def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
                use_original_steps=False, callback=None, *, fs=None, guidance_rescale=0.0, cfg_img=None,
                unconditional_conditioning_img_nonetext=None, noises=None, temperature=1., mask=None, x0=None,
-               q_noises=None, use_graph=False, img_callback=None, log_every_t=100):
+               q_noises=None, use_graph=False, img_callback=None, log_every_t=100, freeu=None):
         """ddim.py:281-301: run the last t_start DDIM steps from x_latent (at level ddim_alphas[t_start - 1]) and return
         the result. The steps are those of `sample`, on the same path (a partial FusedRun when the model has the batched
         entry), so the keyword-only options mean what they mean there; `noises` / `q_noises` are [t_start, ...], indexed
@@ -589,10 +623,11 @@ class DDIMSampler(object):
                                  img_callback=img_callback, log_every_t=log_every_t, temperature=temperature,
                                  unconditional_guidance_scale=unconditional_guidance_scale,
                                  unconditional_conditioning=unconditional_conditioning, fs=fs,
-                                 guidance_rescale=guidance_rescale, noises=noises, use_graph=use_graph, **kw)
+                                 guidance_rescale=guidance_rescale, noises=noises, use_graph=use_graph, freeu=freeu, **kw)
         return x_dec
 
     @torch.no_grad()
+    @_takes_freeu
     def encode(self, x0, c, t_enc, use_original_steps=False, return_intermediates=None,
                unconditional_guidance_scale=1.0, unconditional_conditioning=None, callback=None, *, fs=None,
                guidance_rescale=0.0, use_graph=False, **kwargs):

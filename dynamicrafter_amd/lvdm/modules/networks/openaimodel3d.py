@@ -184,6 +184,27 @@ def _shape_table(cfg):
     return t
 
 
+def cat_plan(layout):
+    """[(channels of h, channels of the skip)] per up block of a _block_layout."""
+    down_path, middle, up_path = layout
+    out_ch = lambda blk: [a.get("cout", a.get("ch")) for k, a in blk if k in ("conv_in", "res", "down", "up")][-1]
+    widths = [out_ch(b) for b in down_path]
+    ch = out_ch(middle)
+    plan = []
+    for blk in up_path:
+        skip = widths.pop()
+        assert blk[0][1]["cin"] == ch + skip
+        plan.append((ch, skip))
+        ch = out_ch(blk)
+    return plan
+
+
+def freeu_stages(plan, model_channels):
+    """Per up block of a cat_plan the FreeU stage that applies: 1 where h has 4 * model_channels channels, 2 where it has
+    2 * model_channels, else None (diffusers keys on 1280 / 640, which is this rule on the SD-2.1 layout)."""
+    return [1 if ch == 4 * model_channels else 2 if ch == 2 * model_channels else None for ch, _ in plan]
+
+
 _Arena = ops.Arena
 
 
@@ -239,23 +260,50 @@ class UNetModel(nn.Module):
         # producers write straight into their column range of one buffer per up block (no torch.cat copy,
         # reference openaimodel3d.py:596): _cat_plan[u] = (channels of h, channels of the skip)
         self._cat_plan = self._make_cat_plan()
+        self._freeu = None                      # enable_freeu's arguments; None: not one launch is added
         attach_params(self, _shape_table(self._cfg))
         self._packed = None
         self._arena = _Arena()
         self.register_load_state_dict_post_hook(lambda m, k: setattr(m, "_packed", None))
 
     def _make_cat_plan(self):
-        down_path, middle, up_path = self._layout
-        out_ch = lambda blk: [a.get("cout", a.get("ch")) for k, a in blk if k in ("conv_in", "res", "down", "up")][-1]
-        widths = [out_ch(b) for b in down_path]
-        ch = out_ch(middle)
-        plan = []
-        for blk in up_path:
-            skip = widths.pop()
-            assert blk[0][1]["cin"] == ch + skip
-            plan.append((ch, skip))
-            ch = out_ch(blk)
-        return plan
+        return cat_plan(self._layout)
+
+    # ------------------------------------------------------------------ FreeU
+    def enable_freeu(self, s1, s2, b1, b2, version=1):
+        """FreeU (Si et al., CVPR 2024), diffusers' argument order: in the decoder, stage 1 (s1, b1) acts on the up blocks
+        whose h has 4 * model_channels channels (1280 on the released configs) and stage 2 (s2, b2) on those with
+        2 * model_channels (640). The skip features get fourier_filter(threshold=1, scale=s), the first half of h's channels
+        are scaled by b (version 1) or by (b-1) * mhat + 1 with mhat the per-frame min-max normalised channel mean of h
+        (version 2, the authors' current form; mhat = 0 for a frame whose mean is flat, where the published code divides by
+        zero). Runs as HIP kernels in place on the [h | skip] buffer ahead of each selected up block (ops.freeu).
+
+        The four numbers are host constants of the launches: a graph-captured run (FusedRun and what builds on it) keeps
+        the setting it was captured with until it is re-created; eager calls see a change at once."""
+        vals = dict(s1=s1, s2=s2, b1=b1, b2=b2)
+        for k, v in vals.items():
+            if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+                raise ValueError(f"enable_freeu: {k} must be a finite number, got {v!r}")
+        if isinstance(version, bool) or version not in (1, 2):
+            raise ValueError(f"enable_freeu: version must be 1 or 2, got {version!r}")
+        self._freeu = dict({k: float(v) for k, v in vals.items()}, version=int(version))
+
+    def disable_freeu(self):
+        self._freeu = None
+
+    @property
+    def freeu(self):
+        """The enable_freeu arguments in force (a dict copy), or None."""
+        return None if self._freeu is None else dict(self._freeu)
+
+    def set_freeu(self, cfg):
+        """enable_freeu(**cfg) or, for None, disable_freeu(); returns the previous setting (what restores it)."""
+        prev = self.freeu
+        if cfg is None:
+            self.disable_freeu()
+        else:
+            self.enable_freeu(**cfg)
+        return prev
 
     # ------------------------------------------------------------------ weights -> device layout
     def _p(self, name):
@@ -676,12 +724,19 @@ class UNetModel(nn.Module):
             else:
                 h = self._run_block(blk, Wt["in"][i], h, g, f"in{i}", final=skip_dst(i))
         h = self._run_block(middle, Wt["mid"], h, g, "mid", final=lambda rows, cols: cat_view(0, rows, "h"))
+        fu = self._freeu
+        fu_stages = freeu_stages(self._cat_plan, mc) if fu is not None else [None] * n_up
         for i, blk in enumerate(up_path):
             ch, cs = self._cat_plan[i]
             if cat_rows.get(i) != h.shape[0]:
                 raise ValueError("skip / decoder resolution mismatch (the latent height and width must divide by 8)")
             cat = A.get(f"cat{i}", h.shape[0], ch + cs, device=dev)
             assert h.data_ptr() == cat.data_ptr() and h.shape[1] == ch
+            stage = fu_stages[i]
+            if stage is not None:
+                n_scr = ops.freeu_scratch_floats(cs=cs, F=g["F"], H=g["H"], W=g["W"], version=fu["version"])
+                ops.freeu(cat, ch=ch, cs=cs, F=g["F"], H=g["H"], W=g["W"], b=fu[f"b{stage}"], s=fu[f"s{stage}"],
+                          version=fu["version"], scratch=A.get(f"freeu{i}", n_scr, 1, torch.float32, dev))
             nxt = (lambda rows, cols, u=i + 1: cat_view(u, rows, "h")) if i + 1 < n_up else None
             h = self._run_block(blk, Wt["out"][i], cat, g, f"out{i}", final=nxt)
         n = self._gn(h, Wt["out_gn"], "gn", n_inst=g["F"], rpi=g["HW"], eps=1e-5, silu=True)

@@ -727,6 +727,55 @@ def add_rows(a, b, y):
     return y
 
 
+def freeu_scratch_floats(*, cs, F, H, W, version=1):
+    """fp32 elements of freeu's `scratch`: the seven sums per (frame, skip channel), as partial sums over up to 8 slices of
+    a large plane; version 2 adds the row means of h and a (min, max) pair per frame. Its contents need no initialisation."""
+    n = int(_hip.lib().dc_freeu_scratch_floats(cs, F, H, W, version))
+    if n < 0:
+        raise ValueError(f"freeu_scratch_floats: bad arguments cs={cs} F={F} H={H} W={W} version={version}")
+    return n
+
+
+def freeu(cat, *, ch, cs, F, H, W, b, s, version=1, scratch):
+    """FreeU in place on cat = [h | skip] (bf16 rows [F*H*W, ch + cs], rows ordered frame, y, x; a column slice of a wider
+    buffer is fine): the skip columns get fourier_filter(x, threshold=1, scale=s) per (frame, channel) plane, the first ch/2
+    columns of h are scaled by b (version 1) or by (b-1)*mhat + 1 (version 2: mhat = the row mean of h over all ch columns,
+    min-max normalised per frame; 0 for a frame whose mean is flat, where the published code divides by zero). Columns
+    ch/2..ch-1 are not touched. 2 launches (version 2: 3), no atomics: bit-reproducible and graph-capturable.
+    scratch: fp32, freeu_scratch_floats(...) elements, from the caller's arena."""
+    _rows(cat, "cat")
+    if version not in (1, 2):
+        raise ValueError(f"freeu: version must be 1 or 2, got {version!r}")
+    if cs < 64 or cs % 64 or ch < 128 or ch % 128:
+        raise ValueError(f"freeu: needs cs % 64 == 0 and ch % 128 == 0, got ch={ch} cs={cs}")
+    if min(F, H, W) < 1 or cat.shape[0] != F * H * W or cat.shape[1] != ch + cs:
+        raise ValueError(f"freeu: cat is {tuple(cat.shape)}, expected [F*H*W, ch+cs] = [{F * H * W}, {ch + cs}]")
+    if cat.stride(0) % 8 or cat.data_ptr() % 16:
+        raise ValueError(f"freeu: cat needs a row stride that is a multiple of 8 and a 16-byte aligned start, got stride "
+                         f"{cat.stride(0)}, address % 16 = {cat.data_ptr() % 16}")
+    if not (math.isfinite(b) and math.isfinite(s)):
+        raise ValueError(f"freeu: b and s must be finite, got b={b} s={s}")
+    if scratch.dtype != torch.float32 or not scratch.is_cuda or not scratch.is_contiguous():
+        raise ValueError("freeu: scratch must be a contiguous CUDA float32 tensor")
+    _need(scratch, freeu_scratch_floats(cs=cs, F=F, H=H, W=W, version=version), "scratch")
+    l = _hip.lib()
+    rows, ld = F * H * W, cat.stride(0)
+    geo = (_ptr(cat), ld, ch, cs, F, H, W)
+    n_stats = freeu_scratch_floats(cs=cs, F=F, H=H, W=W, version=1)
+    stats = C.c_void_p(scratch.data_ptr())
+    hmean = mm = C.c_void_p(0)
+    tag = f"F{F} {H}x{W} ch{ch} cs{cs}"             # per-shape rows of a Tracer's detail table (tools/freeu_ab.py)
+    if version == 2:
+        hmean = C.c_void_p(scratch.data_ptr() + 4 * n_stats)
+        mm = C.c_void_p(scratch.data_ptr() + 4 * (n_stats + rows))
+        _launch("freeu_hmean", 0.0, 2.0 * rows * ch + 4.0 * rows, l.dc_freeu_hmean, *geo, hmean, stream_ptr(), tag=tag)
+    _launch("freeu_skip_stats", 0.0, 2.0 * rows * cs + 4.0 * n_stats, l.dc_freeu_skip_stats, *geo, stats, hmean, mm, stream_ptr(),
+            tag=tag)
+    _launch("freeu_apply", 0.0, 4.0 * rows * (cs + ch // 2), l.dc_freeu_apply, *geo, stats, float(b), float(s), hmean, mm,
+            stream_ptr(), tag=tag)
+    return cat
+
+
 def build_context(ctx, out, *, B, T, n_text, L, D):
     _need(ctx, B * (n_text + T * L) * D, "context"); _need(out, B * T * (n_text + L) * D, "out")
     check(_hip.lib().dc_build_context(_ptr(ctx), _ptr(out), B, T, n_text, L, D, stream_ptr()), "dc_build_context")

@@ -27,7 +27,7 @@ from .inference import get_latent_z, load_model_checkpoint, load_prompts  # noqa
 
 @torch.no_grad()
 def batch_ddim_sampling(model, cond, noise_shape, n_samples=1, ddim_steps=50, ddim_eta=1.0, cfg_scale=1.0,
-                        temporal_cfg_scale=None, **kwargs):
+                        temporal_cfg_scale=None, freeu=None, **kwargs):
     """funcs.py:14-80. `cond` is {"c_crossattn": [...], "c_concat": [...], "fs": tensor}; "fs" is taken out of it (the caller's
     dict comes back without it, as in the reference). A latent width of 32 (the 256 model) samples with "uniform" spacing and no
     guidance rescale, any other width with "uniform_trailing" and 0.7. With cfg_scale != 1 the unconditional branch is a copy of
@@ -37,7 +37,11 @@ def batch_ddim_sampling(model, cond, noise_shape, n_samples=1, ddim_steps=50, dd
     The reference also hands `temporal_length=` and `conditional_guidance_scale_temporal=temporal_cfg_scale` to the sampler, where
     its UNet swallows them unused; they are not forwarded here and `temporal_cfg_scale` has no effect. Every other keyword
     argument reaches `DDIMSampler.sample` (`x_T`, `noises`, `use_graph`, `window_stride`, ...), except `sampler=`, which picks
-    the sampler class as in `image_guided_synthesis` ("ddim", "dpmpp_2m", "dpmpp_2m_sde")."""
+    the sampler class as in `image_guided_synthesis` ("ddim", "dpmpp_2m", "dpmpp_2m_sde").
+    `freeu` (not in the reference): None, or dict(s1=, s2=, b1=, b2=, version=) - FreeU on the UNet's decoder for this call
+    (UNetModel.enable_freeu); the model's previous setting is back when the call returns or raises."""
+    if freeu is not None:
+        kwargs.update(freeu=freeu)
     name = kwargs.pop("sampler", "ddim")
     if name == "ddim":
         ddim_sampler = DDIMSampler(model)

@@ -120,7 +120,7 @@ def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddi
                            unconditional_guidance_scale=1.0, cfg_img=None, fs=None, text_input=False,
                            multiple_cond_cfg=False, loop=False, interp=False, timestep_spacing="uniform",
                            guidance_rescale=0.0, use_fixed_scheduler=False, sampler="ddim", num_frames=None,
-                           window_stride=None, window_weights="triangle", window_shift=0, **kwargs):
+                           window_stride=None, window_weights="triangle", window_shift=0, freeu=None, **kwargs):
     """inference.py:216-313. Returns [batch, n_samples, c, t, h, w] decoded frames.
 
     `use_fixed_scheduler` is accepted and ignored: the fork's "fixed" sampler only patches sigma so that
@@ -136,7 +136,11 @@ def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddi
     temporal_length // 2): the image latent is repeated over `num_frames` for c_concat, `x_T` / `noises` passed through
     are `num_frames` long, and all frames are decoded. `window_stride` alone asks for windows at the clip's own length.
     Not with `loop` / `interp`: their c_concat is zero on interior frames, so interior windows would see a conditioning
-    the model never met."""
+    the model never met.
+    `freeu` (not in the reference): None, or dict(s1=, s2=, b1=, b2=, version=) - FreeU on the UNet's decoder for this call
+    (UNetModel.enable_freeu); the model's previous setting is back when the call returns or raises."""
+    if freeu is not None:
+        kwargs.update(freeu=freeu)
     T_model = getattr(model, "temporal_length", None)
     if num_frames is not None:
         if loop or interp:
@@ -405,6 +409,8 @@ def run_inference(args, gpu_num, gpu_no, device=None):
     filename_list_rank = [filename_list[i] for i in indices]
 
     extra = {k: getattr(args, k) for k in ("sampler", "num_frames", "window_stride") if getattr(args, k, None) is not None}
+    if freeu_from_args(args) is not None:
+        extra["freeu"] = freeu_from_args(args)
     save_kw = dict(container=getattr(args, "container", "apng"), quality=getattr(args, "quality", 90))
     written = []
     start = time.time()
@@ -463,7 +469,22 @@ def get_parser():
     parser.add_argument("--num_frames", type=int, default=None, help="clip length in latent frames; above the model's "
                         "temporal_length the sampler denoises overlapping windows")
     parser.add_argument("--window_stride", type=int, default=None, help="stride of those windows (default temporal_length // 2)")
+    # the two FreeU flags appear in the namespace only when given (freeu_from_args reads them): without them a run's arguments
+    # are what they were
+    parser.add_argument("--freeu", type=float, nargs=4, default=argparse.SUPPRESS, metavar=("S1", "S2", "B1", "B2"),
+                        help="FreeU on the UNet's decoder, diffusers' argument order (its SD-2.1 suggestion: 0.9 0.2 1.4 1.6); "
+                        "default off")
+    parser.add_argument("--freeu_version", type=int, default=argparse.SUPPRESS, choices=(1, 2), help="FreeU backbone scaling: "
+                        "1 = constant b (default), 2 = b weighted by the normalised channel mean")
     return parser
+
+
+def freeu_from_args(args):
+    """--freeu S1 S2 B1 B2 / --freeu_version as the `freeu=` dict of image_guided_synthesis, or None."""
+    v = getattr(args, "freeu", None)
+    if v is None:
+        return None
+    return dict(s1=v[0], s2=v[1], b1=v[2], b2=v[3], version=getattr(args, "freeu_version", 1))
 
 
 def seed_everything(seed):

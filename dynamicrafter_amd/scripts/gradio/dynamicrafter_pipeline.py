@@ -66,6 +66,14 @@ class DynamiCrafterImg2VideoPipeline:
     def enable_xformers_memory_efficient_attention(self):
         pass
 
+    def enable_freeu(self, s1, s2, b1, b2, version=1):
+        """FreeU on the UNet's decoder for every later call of the pipeline, with diffusers' argument order
+        (UNetModel.enable_freeu; `version=2` is the authors' mean-weighted backbone scaling). Not in the reference class."""
+        self.model.model.diffusion_model.enable_freeu(s1, s2, b1, b2, version=version)
+
+    def disable_freeu(self):
+        self.model.model.diffusion_model.disable_freeu()
+
     def to(self, device, dtype=None):
         """Moves the model. `dtype` other than float32 is refused: the kernels fix their own storage types."""
         if dtype is not None and dtype != torch.float32:

@@ -719,6 +719,35 @@ int dc_mask_blend(float* img, const float* x0, const float* mask, const float* q
                   const float* sqrt_1macp_t, const int32_t* step_index, int index, int64_t n,
                   int64_t noise_step_stride, int clean, void* stream);
 
+/* ---- FreeU (Si et al., CVPR 2024; diffusers enable_freeu) in place on the [h | skip] buffer of an up block ----
+ * cat: bf16 rows [F*H*W][ld], 16-byte aligned, ld % 8 == 0, ld >= ch + cs; columns 0..ch-1 are h, ch..ch+cs-1 the skip;
+ * ch % 128 == 0, cs % 64 == 0, H + W <= 1024, F <= 65535, F*H*W*ld < 2^31 (else DC_ERR_SHAPE). Rows are (frame, y, x).
+ * No atomics and no scratch that needs clearing: every call is capturable and two runs on the same input give the same bits.
+ * replaces diffusers' apply_freeu + fourier_filter (utils/torch_utils.py), which the reference UNet would call ahead of
+ * torch.cat([h, hs.pop()]) (openaimodel3d.py:596).
+ *
+ * dc_freeu_scratch_floats: the fp32 elements of the scratch the three entries share for one buffer: `stats`, then (version 2)
+ * `hmean` [F*H*W] and `mm` [F][2], in this order (DC_ERR_ARG for a bad argument). No initialisation needed.
+ *
+ * dc_freeu_skip_stats: per (frame f, skip channel c) the seven fp32 sums over the plane x[y][x'] with ty = 2 pi y / H,
+ * tx = 2 pi x' / W: sum x * (1, cos ty, sin ty, cos tx, sin tx, cos(ty+tx), sin(ty+tx)) -> stats[z][f][c][0..6]. A plane of
+ * 512 pixels or more is summed in nz = min(8, H*W / 256) slices z by as many workgroups, whose partial sums dc_freeu_apply
+ * adds in the order of z; smaller planes have nz = 1 and stats is [F][cs][7]. With hmean / mm (both or neither; FreeU
+ * version 2) it also writes mm[f][0..1] = min / max of hmean[f*H*W ..] over the frame. */
+int64_t dc_freeu_scratch_floats(int cs, int F, int H, int W, int version);
+int dc_freeu_skip_stats(const uint16_t* cat, int ld, int ch, int cs, int F, int H, int W, float* stats, const float* hmean,
+                        float* mm, void* stream);
+
+/* hmean[row] = mean over the ch columns of h, fp32 [F*H*W] (FreeU version 2: hidden_states.mean(1)). */
+int dc_freeu_hmean(const uint16_t* cat, int ld, int ch, int cs, int F, int H, int W, float* hmean, void* stream);
+
+/* One in-place pass. Skip columns: x + (s-1)/(H*W) * (S0 + Cy cos ty + Sy sin ty + Cx cos tx + Sx sin tx + Cxy cos(ty+tx)
+ * + Sxy sin(ty+tx)) with the sums of dc_freeu_skip_stats: fourier_filter(x, threshold=1, scale=s). Columns 0..ch/2-1:
+ * x * b (hmean == mm == NULL, version 1) or x * ((b-1) * mhat + 1), mhat = (hmean - min_f) / (max_f - min_f) and 0 where
+ * max_f == min_f (version 2). fp32 arithmetic, one rounding to bf16. Columns ch/2..ch-1 are neither read nor written. */
+int dc_freeu_apply(uint16_t* cat, int ld, int ch, int cs, int F, int H, int W, const float* stats, float b, float s,
+                   const float* hmean, const float* mm, void* stream);
+
 /* step_index[0] += 1 (device-side loop counter for the graph-captured sampler). */
 int dc_advance_counter(int32_t* counter, void* stream);
 
