@@ -54,6 +54,15 @@ class DcInvertParams(C.Structure):
     ]
 
 
+class DcApgParams(C.Structure):
+    _fields_ = [
+        ("a_t", C.c_void_p), ("sqrt_one_minus_at", C.c_void_p), ("sqrt_acp_t", C.c_void_p), ("sqrt_1macp_t", C.c_void_p),
+        ("step_index", C.c_void_p),
+        ("index", C.c_int), ("v_param", C.c_int), ("x0_space", C.c_int), ("e_nchw", C.c_int),
+        ("cfg_scale", C.c_float), ("eta", C.c_float), ("norm_threshold", C.c_float), ("momentum", C.c_float),
+    ]
+
+
 class DcDpmParams(C.Structure):
     _fields_ = [
         ("A", C.c_void_p), ("alpha_t", C.c_void_p), ("alpha_p_r", C.c_void_p), ("k", C.c_void_p), ("N", C.c_void_p),
@@ -146,6 +155,9 @@ SIGNATURES = {
     "dc_freeu_skip_stats": (_I, [_P] + [_I] * 6 + [_P, _P, _P, _P]),
     "dc_freeu_hmean": (_I, [_P] + [_I] * 6 + [_P, _P]),
     "dc_freeu_apply": (_I, [_P] + [_I] * 6 + [_P, _F, _F, _P, _P, _P]),
+    "dc_apg_workspace_floats": (_L, [_I] * 3),
+    "dc_apg_reduce": (_I, [C.POINTER(DcApgParams), _P, _P, _I, _P, _P, _I, _I, _I, _P, _P]),
+    "dc_apg_apply": (_I, [C.POINTER(DcApgParams), _P, _I, _P, _P, _P, _I, _I, _I, _I, _P, _P]),
     "dc_advance_counter": (_I, [_P, _P]),
     "dc_stream_create": (_I, [C.POINTER(_P)]),
     "dc_stream_destroy": (_I, [_P]),

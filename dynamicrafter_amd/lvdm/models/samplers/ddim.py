@@ -23,6 +23,11 @@ behaves as the reference's, including the 3-branch guidance of ddim_multiplecond
   * `freeu=dict(s1=, s2=, b1=, b2=, version=)` (not in the reference) on `sample`, `ddim_sampling`, `decode` and `encode`
     runs that call with FreeU on the UNet (UNetModel.enable_freeu) and puts the model's previous setting
     back afterwards, also when the call raises; None (default) leaves the model's setting as it is.
+  * `apg=dict(eta=0.0, norm_threshold=None, momentum=0.0, space="x0")` (not in the reference) on `sample`, `ddim_sampling`
+    and `decode` replaces the CFG combine by adaptive projected guidance (Sadat et al., ICLR 2025): two launches
+    (ops.apg_guide) between the UNet and the unchanged update, which then takes the guided output as its only branch; the
+    running update lives in the run and is zeroed by rewind(). Two branches only, not with guidance_rescale (check_apg,
+    DESIGN 4.13). None (default): nothing is added.
 """
 import contextlib
 import functools
@@ -89,6 +94,67 @@ def _takes_freeu(fn):
         with freeu_scope(self.model, freeu):
             return fn(self, *args, **kwargs)
     return wrapped
+
+
+APG_DEFAULTS = dict(eta=0.0, norm_threshold=None, momentum=0.0, space="x0")
+
+
+def apg_config(apg):
+    """The validated, completed copy of an `apg=` dict (keys of APG_DEFAULTS), or None for None."""
+    if apg is None:
+        return None
+    if not isinstance(apg, dict):
+        raise ValueError(f"apg= takes a dict with keys {sorted(APG_DEFAULTS)} or None, got {type(apg).__name__}")
+    unknown = sorted(set(apg) - set(APG_DEFAULTS))
+    if unknown:
+        raise ValueError(f"apg=: unknown keys {unknown}; known: {sorted(APG_DEFAULTS)}")
+    cfg = dict(APG_DEFAULTS, **apg)
+    for k in ("eta", "momentum", "norm_threshold"):
+        v = cfg[k]
+        if k == "norm_threshold" and v is None:
+            continue
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not np.isfinite(v):
+            raise ValueError(f"apg=: {k} must be a finite number{' or None' if k == 'norm_threshold' else ''}, got {v!r}")
+        cfg[k] = float(v)
+    if cfg["space"] not in ops.APG_SPACES:
+        raise ValueError(f"apg=: space must be one of {ops.APG_SPACES}, got {cfg['space']!r}")
+    return cfg
+
+
+def check_apg(apg, sampler, n_branches, guidance_rescale, three_branch, last=None):
+    """What adaptive projected guidance cannot be combined with, refused before any GPU work; returns apg_config(apg).
+    `last`: the run covers the last `last` steps of the sampler's schedule only (all of them: None)."""
+    apg = apg_config(apg)
+    if apg is None:
+        return None
+    if three_branch or n_branches > 2:
+        raise ValueError("apg= is defined for two guidance branches: not with unconditional_conditioning_img_nonetext / cfg_img")
+    if n_branches < 2:
+        raise ValueError("apg= needs classifier-free guidance: an unconditional_conditioning and a guidance scale other than 1")
+    if guidance_rescale > 0:
+        raise ValueError("apg= replaces guidance_rescale (both counter the saturation of high guidance scales): pass "
+                         "guidance_rescale=0 with it")
+    if apg["space"] == "x0" and sampler.model.parameterization != "v":
+        a = np.asarray(sampler.ddim_alphas, dtype=np.float64)       # ascending DDIM index; a run's steps are the first `last`
+        a = a if last is None else a[:int(last)]
+        if not (a > 0).all():
+            raise ValueError("apg= with space='x0' on an eps model needs a_t > 0 at every step (x0 = (x - sqrt(1-a_t) eps) / "
+                             "sqrt(a_t)); this schedule reaches a_t = 0: use space='model'")
+    return apg
+
+
+def apg_generic(tables, apg, state, e_c, e_u, x, w, *, v_param, index):
+    """Adaptive projected guidance on the generic path: the kernels of the fused path (ops.apg_guide) on the [B, C, ...]
+    outputs of separate apply_model calls, at executed step `index` of `tables`. `state`: a dict that carries the running
+    update and the scratch from call to call (the sampling loop holds one per call; None: a single first step). Returns the
+    guided output, which the update then takes as its only branch."""
+    st = {} if state is None else state
+    geo = dict(B=x.shape[0], Cc=x.shape[1], THW=int(np.prod(x.shape[2:])))
+    if "m" not in st:
+        st.update(m=torch.zeros_like(x), out=torch.empty_like(x),
+                  ws=torch.empty(ops.apg_workspace_floats(**geo), dtype=torch.float32, device=x.device))
+    return ops.apg_guide(tables, e_c, e_u, x, st["m"], st["out"], st["ws"], cfg_scale=float(w), v_param=v_param, index=index,
+                         e_nchw=True, **geo, **apg)
 
 
 def _update_kw(m, x, cfg_scale, cfg_img, guidance_rescale, temperature, **extra):
@@ -172,7 +238,7 @@ class FusedRun(StepRun):
 
     def __init__(self, sampler, img, branches, *, fs=None, noises=None, cfg_scale=1.0, cfg_img=None,
                  guidance_rescale=0.0, temperature=1.0, mask=None, x0=None, q_noises=None, clean_cond=False,
-                 windows=None, last=None):
+                 windows=None, last=None, apg=None):
         # `last`: a partial run over the last n steps of the schedule (decode, timesteps=): the execution-order tables and
         # the timestep table are sliced, so the counter still starts at 0 and noises / q_noises are [n, ...]
         S_all = int(sampler._exec_timesteps.shape[0])
@@ -181,6 +247,9 @@ class FusedRun(StepRun):
             raise ValueError(f"a partial run covers 1 .. {S_all} steps, got {n}")
         if n < S_all and windows is not None:
             raise ValueError("partial runs are not implemented with windows")
+        # `apg`: adaptive projected guidance (apg_config's dict) in place of the CFG combine: two launches between the UNet
+        # and the unchanged update, which then sees the guided rows as a single branch
+        apg = check_apg(apg, sampler, len(branches), guidance_rescale, cfg_img is not None, last=n)
         t_host = torch.as_tensor(sampler._exec_timesteps[S_all - n:].copy(), dtype=torch.int64)
         super().__init__(sampler.model, img, branches, t_host[:, None].expand(-1, img.shape[0]), fs=fs, windows=windows)
         self.sampler = sampler
@@ -189,8 +258,22 @@ class FusedRun(StepRun):
         self.noises, self.blend = _step_inputs(img, self.S, noises, mask, x0, q_noises, clean_cond,
                                                long_branches=None if windows is None else branches)
         self.pred_x0 = torch.empty_like(img)
-        self.kw = _update_kw(self.model, img, cfg_scale, cfg_img, guidance_rescale, temperature,
-                             noise_step_stride=img.numel())
+        self.apg = apg
+        if apg is None:
+            self.kw = _update_kw(self.model, img, cfg_scale, cfg_img, guidance_rescale, temperature,
+                                 noise_step_stride=img.numel())
+        else:
+            # the update takes the guided rows as its only branch
+            self.kw = _update_kw(self.model, img, 1.0, None, 0.0, temperature, noise_step_stride=img.numel())
+            geo = {k: self.kw[k] for k in ("B", "Cc", "THW")}
+            self.apg_kw = dict(geo, v_param=self.kw["v_param"], cfg_scale=float(cfg_scale), **apg)
+            self.apg_m = torch.zeros_like(img)          # the running update m, zero ahead of the first step
+            self.apg_out = torch.empty((geo["B"] * geo["THW"], geo["Cc"]), dtype=torch.float32, device=img.device)
+            self.apg_ws = torch.empty(ops.apg_workspace_floats(**geo), dtype=torch.float32, device=img.device)
+
+    def _reset_state(self):
+        if self.apg is not None:
+            self.apg_m.zero_()                          # capture()'s eager warm-up step wrote it
 
     def _enqueue(self):
         if self.blend is not None:
@@ -201,7 +284,11 @@ class FusedRun(StepRun):
         M = self.kw["B"] * self.kw["THW"]
         e_u = e[M:2 * M] if self.nb > 1 else None
         e_i = e[2 * M:3 * M] if self.nb > 2 else None
-        self._update(e[:M], e_u, e_i)
+        if self.apg is None:
+            self._update(e[:M], e_u, e_i)
+        else:
+            self._update(ops.apg_guide(self.tables, e[:M], e_u, self.img, self.apg_m, self.apg_out, self.apg_ws,
+                                       step_index=self.counter, **self.apg_kw), None, None)
         ops.advance_counter(self.counter)
 
     def _evaluate(self):
@@ -439,7 +526,7 @@ class DDIMSampler(object):
                       noise_dropout=0., score_corrector=None, corrector_kwargs=None, unconditional_guidance_scale=1.,
                       unconditional_conditioning=None, verbose=True, precision=None, fs=None, guidance_rescale=0.0,
                       noises=None, use_graph=False, window_stride=None, window_weights="triangle", window_shift=0,
-                      windows_per_call=None, **kwargs):
+                      windows_per_call=None, apg=None, **kwargs):
         if ddim_use_original_steps or quantize_denoised or score_corrector is not None or noise_dropout > 0.:
             raise NotImplementedError("only the options DynamiCrafter inference uses are implemented "
                                       "(no original-steps / quantised / corrected sampling)")
@@ -450,7 +537,7 @@ class DDIMSampler(object):
                              unconditional_conditioning=unconditional_conditioning, fs=fs,
                              guidance_rescale=guidance_rescale, noises=noises, use_graph=use_graph,
                              window_stride=window_stride, window_weights=window_weights, window_shift=window_shift,
-                             windows_per_call=windows_per_call, **kwargs)
+                             windows_per_call=windows_per_call, apg=apg, **kwargs)
 
     def subset_steps(self, timesteps):
         """How many steps `ddim_sampling(timesteps=k)` runs: the DDIM indices range(S)[:subset_end], descending, with the
@@ -464,11 +551,15 @@ class DDIMSampler(object):
     def _denoise(self, n, cond, shape, x_T=None, callback=None, mask=None, x0=None, img_callback=None, log_every_t=100,
                  temperature=1., unconditional_guidance_scale=1., unconditional_conditioning=None, fs=None,
                  guidance_rescale=0.0, noises=None, use_graph=False, window_stride=None, window_weights="triangle",
-                 window_shift=0, windows_per_call=None, **kwargs):
+                 window_shift=0, windows_per_call=None, apg=None, **kwargs):
         """The last `n` steps of the schedule from x_T (all S of them: ddim_sampling; fewer: timesteps= and decode).
         Executed step i of the n is step S - n + i of the full run and indexes `noises` / `q_noises` ([n, ...]) by i."""
         m = self.model
         dev = m.device
+        if apg is not None:                              # refused combinations: before anything touches the GPU
+            apg = check_apg(apg, self, len(self._branches(cond, unconditional_conditioning, unconditional_guidance_scale,
+                                                          kwargs)), guidance_rescale,
+                            kwargs.get("cfg_img") is not None, last=n or None)
         if dev.type != "cuda":
             raise RuntimeError(f"{type(self).__name__} runs on the HIP path only: put the model on the GPU")
         img = (torch.randn(shape, device=dev) if x_T is None else x_T.to(dev)).to(torch.float32).contiguous().clone()
@@ -510,6 +601,8 @@ class DDIMSampler(object):
                 noises = torch.stack(ns)
         g = dict(temperature=temperature, unconditional_guidance_scale=unconditional_guidance_scale, fs=fs,
                  guidance_rescale=guidance_rescale)
+        if apg is not None:                              # the generic path's running update lives as long as this call
+            g.update(apg=apg, apg_state={})
         intermediates = {"x_inter": [img.clone()], "pred_x0": [img.clone()]}
         run = None
         if hasattr(m, "apply_model_rows") and all(isinstance(c, dict) for c in branches):
@@ -517,7 +610,7 @@ class DDIMSampler(object):
             run = cls(self, img, branches, fs=fs, noises=noises, cfg_scale=unconditional_guidance_scale,
                       cfg_img=kwargs.get("cfg_img"), guidance_rescale=guidance_rescale, temperature=temperature,
                       mask=mask, x0=x0, q_noises=q_noises, clean_cond=clean_cond, **wkw,
-                      **({} if off == 0 else {"last": n}))
+                      **({} if off == 0 else {"last": n}), **({} if apg is None else {"apg": apg}))
             if use_graph:
                 run.capture()
         else:
@@ -561,8 +654,10 @@ class DDIMSampler(object):
                       temperature=1., noise_dropout=0., score_corrector=None, corrector_kwargs=None,
                       unconditional_guidance_scale=1., unconditional_conditioning=None, uc_type=None,
                       conditional_guidance_scale_temporal=None, mask=None, x0=None, guidance_rescale=0.0, noise=None,
-                      cfg_img=None, model=None, **kwargs):
-        """One DDIM update from separate apply_model calls (reference :205-279 / multiplecond :211-285)."""
+                      cfg_img=None, model=None, apg=None, apg_state=None, **kwargs):
+        """One DDIM update from separate apply_model calls (reference :205-279 / multiplecond :211-285). `apg`: adaptive
+        projected guidance (apg_generic) ahead of the same kernel; `apg_state`: a dict that carries the running update from
+        call to call (None: this call is a first step)."""
         if use_original_steps or quantize_denoised or score_corrector is not None or noise_dropout > 0.:
             raise NotImplementedError
         m = self.model if model is None else model
@@ -584,6 +679,12 @@ class DDIMSampler(object):
                 noise = noise[:1].expand_as(x)
         noise = noise.to(torch.float32).contiguous()
         x_prev, pred_x0 = torch.empty_like(x), torch.empty_like(x)
+        if apg is not None:
+            apg = check_apg(apg, self, 1 + (e_u is not None) + (e_i is not None), guidance_rescale,
+                            cfg_img is not None or uc2 is not None)
+            e_c = apg_generic(self._tables, apg, apg_state, e_c, e_u, x, unconditional_guidance_scale,
+                              v_param=m.parameterization == "v", index=S - 1 - index)
+            e_u, unconditional_guidance_scale = None, 1.0
         return ops.ddim_step(self._tables, e_c, e_u, e_i, x, noise, x_prev, pred_x0, ops.step_workspace(x.shape[0], dev),
                              index=S - 1 - index, e_nchw=True,
                              **_update_kw(m, x, unconditional_guidance_scale, cfg_img, guidance_rescale, temperature))
@@ -604,7 +705,7 @@ class DDIMSampler(object):
     def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
                use_original_steps=False, callback=None, *, fs=None, guidance_rescale=0.0, cfg_img=None,
                unconditional_conditioning_img_nonetext=None, noises=None, temperature=1., mask=None, x0=None,
-               q_noises=None, use_graph=False, img_callback=None, log_every_t=100, freeu=None):
+               q_noises=None, use_graph=False, img_callback=None, log_every_t=100, freeu=None, apg=None):
         """ddim.py:281-301: run the last t_start DDIM steps from x_latent (at level ddim_alphas[t_start - 1]) and return
         the result. The steps are those of `sample`, on the same path (a partial FusedRun when the model has the batched
         entry), so the keyword-only options mean what they mean there; `noises` / `q_noises` are [t_start, ...], indexed
@@ -623,7 +724,8 @@ class DDIMSampler(object):
                                  img_callback=img_callback, log_every_t=log_every_t, temperature=temperature,
                                  unconditional_guidance_scale=unconditional_guidance_scale,
                                  unconditional_conditioning=unconditional_conditioning, fs=fs,
-                                 guidance_rescale=guidance_rescale, noises=noises, use_graph=use_graph, freeu=freeu, **kw)
+                                 guidance_rescale=guidance_rescale, noises=noises, use_graph=use_graph, freeu=freeu, apg=apg,
+                                 **kw)
         return x_dec
 
     @torch.no_grad()
@@ -640,6 +742,8 @@ class DDIMSampler(object):
         with return_intermediates = r the latent and pred_x0 after every max(t_enc // r, 1)-th step and after the last."""
         if use_original_steps:
             raise NotImplementedError("encode runs on the DDIM timesteps only")
+        if "apg" in kwargs:
+            raise ValueError("encode: apg= is a sampling-time guidance with a running state; an inversion under it is not defined")
         if kwargs.get("window_stride") is not None:
             raise ValueError("encode: windowed (long-clip) inversion is not defined")
         S = self.ddim_timesteps.shape[0]

@@ -3,7 +3,8 @@
 `DPMSolverSampler(model, solver="dpmpp_2m" | "dpmpp_2m_sde").sample(...)` takes the arguments of `DDIMSampler.sample`
 and returns the same `(samples, intermediates)`. It runs on the DDIM timesteps of `timestep_spacing` ("uniform",
 "uniform_trailing", "quad") and evaluates the model exactly as DDIM does (batched cond / uncond / image-only branches,
-CFG, guidance rescale, v or eps parameterisation, dynamic rescale, mask / x0 blending, hipGraph capture).
+CFG or adaptive projected guidance (`apg=`), guidance rescale, v or eps parameterisation, dynamic rescale, mask / x0
+blending, hipGraph capture).
 
 Per executed step i, with alpha = sqrt(ddim_alphas), sigma = sqrt(1 - ddim_alphas) at t (suffix t) and at the DDIM
 "prev" timestep (suffix p), lambda = log(alpha / sigma), h_i = lambda_p - lambda_t, r_i = scale_arr_prev / scale_arr
@@ -26,7 +27,7 @@ import numpy as np
 import torch
 
 from .... import ops
-from .ddim import DDIMSampler, FusedRun, _update_kw
+from .ddim import DDIMSampler, FusedRun, _update_kw, apg_generic
 
 SOLVERS = ("dpmpp_2m", "dpmpp_2m_sde")
 LOWER_ORDER_FINAL_BELOW = 15
@@ -74,6 +75,7 @@ class DpmRun(FusedRun):
                        self.x0_hist, step_index=self.counter, **self.kw)
 
     def _reset_state(self):
+        super()._reset_state()
         self.x0_hist.zero_()                            # capture()'s eager warm-up step wrote slot 0
 
 
@@ -117,13 +119,18 @@ class DPMSolverSampler(DDIMSampler):
         m, dev = self.model if model is None else model, img.device
         hist = torch.zeros((2,) + tuple(img.shape), dtype=torch.float32, device=dev)
         ws = ops.step_workspace(img.shape[0], dev)
-        kw = _update_kw(m, img, g["unconditional_guidance_scale"], kwargs.get("cfg_img"), g["guidance_rescale"],
+        apg, state = g.get("apg"), g.get("apg_state")   # checked by the caller: two branches, no guidance rescale
+        w = g["unconditional_guidance_scale"]
+        kw = _update_kw(m, img, w if apg is None else 1.0, kwargs.get("cfg_img"), g["guidance_rescale"],
                         g["temperature"], e_nchw=True)
+        v_param = m.parameterization == "v"
 
         def update(img, i, noise):
             ts = torch.full((img.shape[0],), int(self._exec_timesteps[i]), device=dev, dtype=torch.long)
             e = [m.apply_model(img, ts, c, fs=g["fs"]).to(torch.float32).contiguous() for c in branches]
             e += [None] * (3 - len(e))
+            if apg is not None:                         # adaptive projected guidance, then a single branch
+                e[0], e[1] = apg_generic(self._tables, apg, state, e[0], e[1], img, w, v_param=v_param, index=i), None
             return ops.dpmpp_step(self._tables, e[0], e[1], e[2], img, noise, torch.empty_like(img),
                                   torch.empty_like(img), ws, hist, index=i, **kw)
         return update

@@ -919,6 +919,86 @@ def dpmpp_step(tables, e_cond, e_uncond, e_img, x, noise, x_prev, pred_x0, works
     return x_prev, pred_x0
 
 
+APG_SPACES = ("x0", "model")
+
+
+def apg_workspace_floats(*, B, Cc, THW):
+    """fp32 elements of apg_guide's `workspace` for B clips of Cc x THW elements: three partial sums per workgroup of the
+    reduction (min(256, ceil(THW / 256)) workgroups per clip). Its contents need no initialisation."""
+    n = int(_hip.lib().dc_apg_workspace_floats(B, Cc, THW))
+    if n < 0:
+        raise ValueError(f"apg_workspace_floats: bad arguments B={B} Cc={Cc} THW={THW}")
+    return n
+
+
+def apg_guide(tables, e_cond, e_uncond, x, momentum_buf, out, workspace, *, B, Cc, THW, cfg_scale, eta, norm_threshold,
+              momentum, space, v_param, index=0, step_index=None, e_nchw=False, ld_e=None):
+    """Adaptive projected guidance (dc_apg_reduce + dc_apg_apply) in place of the CFG combine: `out` = the guided model
+    output, which ddim_step / dpmpp_step then take as e_cond with e_uncond=None and cfg_scale=1. e_cond, e_uncond and out:
+    fp32 rows [B*THW, ld] (out may have a row stride of its own) or [B, Cc, THW] under e_nchw; x and momentum_buf: fp32
+    [B, Cc, THW]. momentum_buf is the running update m, changed in place: zero it ahead of the first step of a run (with
+    momentum == 0 it is only written). space "x0" projects in the space of the denoised prediction (tables: sqrt_acp_t and
+    sqrt_1macp_t for v models, a_t and sqrt_one_minus_at for eps models, indexed by the step), "model" on the raw outputs.
+    norm_threshold None or <= 0: no clipping. workspace: apg_workspace_floats(...) fp32 elements."""
+    if space not in APG_SPACES:
+        raise ValueError(f"apg_guide: space must be one of {APG_SPACES}, got {space!r}")
+    for nm, v in (("cfg_scale", cfg_scale), ("eta", eta), ("momentum", momentum),
+                  ("norm_threshold", 0.0 if norm_threshold is None else norm_threshold)):
+        if isinstance(v, bool) or not isinstance(v, (int, float)) or not math.isfinite(v):
+            raise ValueError(f"apg_guide: {nm} must be a finite number, got {v!r}")
+    if e_uncond is None:
+        raise ValueError("apg_guide: needs e_uncond (guidance with two branches)")
+    n = B * Cc * THW
+    if min(B, Cc, THW) < 1 or B > 65535:
+        raise ValueError(f"apg_guide: bad shape B={B} Cc={Cc} THW={THW} (1 <= B <= 65535)")
+    if ld_e is None:
+        ld_e = 0 if e_nchw else e_cond.stride(0)
+    ld_out = 0 if e_nchw else (out.stride(0) if out.dim() == 2 else Cc)
+    if not e_nchw and (ld_e < Cc or ld_out < Cc):
+        raise ValueError(f"apg_guide: row strides {ld_e} / {ld_out} are below the {Cc} channels")
+    for t, nm in ((e_cond, "e_cond"), (e_uncond, "e_uncond"), (x, "x"), (momentum_buf, "momentum_buf"), (out, "out"),
+                  (workspace, "workspace")):
+        if t is None:
+            if nm == "x" and space == "model":
+                continue
+            raise ValueError(f"apg_guide: {nm} is missing")
+        if t.dtype != torch.float32 or not t.is_cuda:
+            raise ValueError(f"apg_guide: {nm} must be a CUDA float32 tensor, got {t.dtype} on {t.device}")
+    for t, nm in ((x, "x"), (momentum_buf, "momentum_buf"), (workspace, "workspace")):
+        if t is not None and not t.is_contiguous():
+            raise ValueError(f"apg_guide: {nm} must be contiguous")
+    _need(x, n, "x"); _need(momentum_buf, n, "momentum_buf")
+    _need(workspace, apg_workspace_floats(B=B, Cc=Cc, THW=THW), "workspace")
+    for t, nm in ((e_cond, "e_cond"), (e_uncond, "e_uncond")):
+        _need(t, n if e_nchw else (B * THW - 1) * ld_e + Cc, nm)
+    # out may be a column slice of a wider buffer: what counts is the storage behind its first element
+    room = out.untyped_storage().nbytes() // 4 - out.storage_offset()
+    if room < (n if e_nchw else (B * THW - 1) * ld_out + Cc):
+        raise ValueError(f"out: {room} elements from its start, the launch writes {n if e_nchw else (B * THW - 1) * ld_out + Cc}")
+    p = _hip.DcApgParams()
+    x0 = space == "x0"
+    need = (("sqrt_acp_t", "sqrt_1macp_t") if v_param else ("a_t", "sqrt_one_minus_at")) if x0 else ()
+    for k in ("a_t", "sqrt_one_minus_at", "sqrt_acp_t", "sqrt_1macp_t"):
+        t = tables.get(k) if k in need else None
+        if k in need:
+            if t is None or t.dtype != torch.float32 or not t.is_contiguous():
+                raise ValueError(f"apg_guide: table {k} must be a contiguous fp32 vector (space='x0')")
+            if step_index is None and not 0 <= index < t.numel():
+                raise ValueError(f"apg_guide: step {index} is outside table {k}'s {t.numel()} steps")
+        setattr(p, k, 0 if t is None else t.data_ptr())
+    p.step_index = 0 if step_index is None else step_index.data_ptr()
+    p.index, p.v_param, p.x0_space, p.e_nchw = index, 1 if v_param else 0, 1 if x0 else 0, 1 if e_nchw else 0
+    p.cfg_scale, p.eta, p.momentum = cfg_scale, eta, momentum
+    p.norm_threshold = 0.0 if norm_threshold is None else norm_threshold
+    l = _hip.lib()
+    xp = _ptr(x if x0 else None)
+    _launch("apg_reduce", 3.0 * n, 4.0 * n * (5 if x0 else 4), l.dc_apg_reduce, C.byref(p), _ptr(e_cond), _ptr(e_uncond), ld_e,
+            xp, _ptr(momentum_buf), B, Cc, THW, _ptr(workspace), stream_ptr())
+    _launch("apg_apply", 3.0 * n, 4.0 * n * (4 if x0 else 3), l.dc_apg_apply, C.byref(p), _ptr(e_cond), ld_e, xp,
+            _ptr(momentum_buf), _ptr(out), ld_out, B, Cc, THW, _ptr(workspace), stream_ptr())
+    return out
+
+
 SDS_WEIGHT_TYPES = ("t", "ada", "uniform")
 SDS_X0_FORMULAS = ("reference", "parameterization")
 

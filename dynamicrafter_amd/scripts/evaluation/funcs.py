@@ -27,7 +27,7 @@ from .inference import get_latent_z, load_model_checkpoint, load_prompts  # noqa
 
 @torch.no_grad()
 def batch_ddim_sampling(model, cond, noise_shape, n_samples=1, ddim_steps=50, ddim_eta=1.0, cfg_scale=1.0,
-                        temporal_cfg_scale=None, freeu=None, **kwargs):
+                        temporal_cfg_scale=None, freeu=None, apg=None, **kwargs):
     """funcs.py:14-80. `cond` is {"c_crossattn": [...], "c_concat": [...], "fs": tensor}; "fs" is taken out of it (the caller's
     dict comes back without it, as in the reference). A latent width of 32 (the 256 model) samples with "uniform" spacing and no
     guidance rescale, any other width with "uniform_trailing" and 0.7. With cfg_scale != 1 the unconditional branch is a copy of
@@ -39,9 +39,14 @@ def batch_ddim_sampling(model, cond, noise_shape, n_samples=1, ddim_steps=50, dd
     argument reaches `DDIMSampler.sample` (`x_T`, `noises`, `use_graph`, `window_stride`, ...), except `sampler=`, which picks
     the sampler class as in `image_guided_synthesis` ("ddim", "dpmpp_2m", "dpmpp_2m_sde").
     `freeu` (not in the reference): None, or dict(s1=, s2=, b1=, b2=, version=) - FreeU on the UNet's decoder for this call
-    (UNetModel.enable_freeu); the model's previous setting is back when the call returns or raises."""
+    (UNetModel.enable_freeu); the model's previous setting is back when the call returns or raises.
+    `apg` (not in the reference): None, or dict(eta=0.0, norm_threshold=None, momentum=0.0, space="x0") - adaptive projected
+    guidance in place of the plain CFG combine (lvdm/models/samplers/ddim.py); it needs cfg_scale != 1, and it
+    takes the place of the guidance rescale of 0.7, which is then not applied."""
     if freeu is not None:
         kwargs.update(freeu=freeu)
+    if apg is not None:
+        kwargs.update(apg=apg)
     name = kwargs.pop("sampler", "ddim")
     if name == "ddim":
         ddim_sampler = DDIMSampler(model)
@@ -57,7 +62,7 @@ def batch_ddim_sampling(model, cond, noise_shape, n_samples=1, ddim_steps=50, dd
     if noise_shape[-1] == 32:
         timestep_spacing, guidance_rescale = "uniform", 0.0
     else:
-        timestep_spacing, guidance_rescale = "uniform_trailing", 0.7
+        timestep_spacing, guidance_rescale = "uniform_trailing", 0.7 if apg is None else 0.0
 
     if cfg_scale != 1.0:
         if model.uncond_type == "empty_seq":

@@ -120,7 +120,8 @@ def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddi
                            unconditional_guidance_scale=1.0, cfg_img=None, fs=None, text_input=False,
                            multiple_cond_cfg=False, loop=False, interp=False, timestep_spacing="uniform",
                            guidance_rescale=0.0, use_fixed_scheduler=False, sampler="ddim", num_frames=None,
-                           window_stride=None, window_weights="triangle", window_shift=0, freeu=None, **kwargs):
+                           window_stride=None, window_weights="triangle", window_shift=0, freeu=None, apg=None,
+                           **kwargs):
     """inference.py:216-313. Returns [batch, n_samples, c, t, h, w] decoded frames.
 
     `use_fixed_scheduler` is accepted and ignored: the fork's "fixed" sampler only patches sigma so that
@@ -138,9 +139,14 @@ def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddi
     Not with `loop` / `interp`: their c_concat is zero on interior frames, so interior windows would see a conditioning
     the model never met.
     `freeu` (not in the reference): None, or dict(s1=, s2=, b1=, b2=, version=) - FreeU on the UNet's decoder for this call
-    (UNetModel.enable_freeu); the model's previous setting is back when the call returns or raises."""
+    (UNetModel.enable_freeu); the model's previous setting is back when the call returns or raises.
+    `apg` (not in the reference): None, or dict(eta=0.0, norm_threshold=None, momentum=0.0, space="x0") - adaptive projected
+    guidance in place of the plain CFG combine (lvdm/models/samplers/ddim.py). Two guidance branches only, and
+    not with guidance_rescale > 0."""
     if freeu is not None:
         kwargs.update(freeu=freeu)
+    if apg is not None:
+        kwargs.update(apg=apg)
     T_model = getattr(model, "temporal_length", None)
     if num_frames is not None:
         if loop or interp:
@@ -411,6 +417,8 @@ def run_inference(args, gpu_num, gpu_no, device=None):
     extra = {k: getattr(args, k) for k in ("sampler", "num_frames", "window_stride") if getattr(args, k, None) is not None}
     if freeu_from_args(args) is not None:
         extra["freeu"] = freeu_from_args(args)
+    if apg_from_args(args) is not None:
+        extra["apg"] = apg_from_args(args)
     save_kw = dict(container=getattr(args, "container", "apng"), quality=getattr(args, "quality", 90))
     written = []
     start = time.time()
@@ -476,7 +484,21 @@ def get_parser():
                         "default off")
     parser.add_argument("--freeu_version", type=int, default=argparse.SUPPRESS, choices=(1, 2), help="FreeU backbone scaling: "
                         "1 = constant b (default), 2 = b weighted by the normalised channel mean")
+    # likewise --apg / --apg_space (apg_from_args)
+    parser.add_argument("--apg", type=float, nargs=3, default=argparse.SUPPRESS, metavar=("ETA", "NORM_THRESHOLD", "MOMENTUM"),
+                        help="adaptive projected guidance in place of plain CFG (the paper's suggestion for SDXL-class models: "
+                        "0 15 -0.5); NORM_THRESHOLD <= 0 switches the clipping off; needs --guidance_rescale 0; default off")
+    parser.add_argument("--apg_space", type=str, default=argparse.SUPPRESS, choices=("x0", "model"), help="where APG projects: "
+                        "x0 = the denoised prediction (default, the paper), model = the raw output (diffusers)")
     return parser
+
+
+def apg_from_args(args):
+    """--apg ETA NORM_THRESHOLD MOMENTUM / --apg_space as the `apg=` dict of image_guided_synthesis, or None."""
+    v = getattr(args, "apg", None)
+    if v is None:
+        return None
+    return dict(eta=v[0], norm_threshold=v[1] if v[1] > 0 else None, momentum=v[2], space=getattr(args, "apg_space", "x0"))
 
 
 def freeu_from_args(args):

@@ -175,9 +175,13 @@ class DynamiCrafterImg2VideoPipeline:
     def __call__(self, image, prompt="", negative_prompt=None, num_inference_steps=50, guidance_scale=7.5, eta=0.0,
                  frame_stride=3, num_frames=None, height=None, width=None, num_videos_per_prompt=1, generator=None,
                  latents=None, output_type="tensor", return_dict=True, callback=None, callback_steps=1,
-                 cross_attention_kwargs=None, **kwargs):
+                 cross_attention_kwargs=None, apg=None, **kwargs):
         """:398-530. Returns {"videos": v} (or v with return_dict=False); v is [b, 3, num_frames, height, width] as a device
-        tensor ("tensor"), an ndarray ("numpy") or b lists of PIL frames ("pil"). Extra **kwargs reach DDIMSampler.sample."""
+        tensor ("tensor"), an ndarray ("numpy") or b lists of PIL frames ("pil"). Extra **kwargs reach DDIMSampler.sample.
+        `apg` (not in the reference): dict(eta=0.0, norm_threshold=None, momentum=0.0, space="x0") for adaptive projected
+        guidance in place of plain CFG (DDIMSampler.sample's `apg=`); needs guidance_scale != 1."""
+        if apg is not None:
+            kwargs["apg"] = apg
         if isinstance(prompt, str):
             prompt = [prompt]
         batch_size = len(prompt)

@@ -748,6 +748,53 @@ int dc_freeu_hmean(const uint16_t* cat, int ld, int ch, int cs, int F, int H, in
 int dc_freeu_apply(uint16_t* cat, int ld, int ch, int cs, int F, int H, int W, const float* stats, float b, float s,
                    const float* hmean, const float* mm, void* stream);
 
+/* ---- Adaptive projected guidance (APG: Sadat, Hilliges, Weber, ICLR 2025, Algorithm 1) ahead of a step's update kernel ---- */
+typedef struct DcApgParams {
+    /* per-step fp32 tables in execution order (DcDdimParams'), read only with x0_space and indexed by step_index[0] (device)
+     * when step_index != NULL, else by `index` */
+    const float* a_t;                /* eps models: x0 = (x - sqrt_one_minus_at eps) / sqrt(a_t); a_t > 0 is the caller's duty */
+    const float* sqrt_one_minus_at;
+    const float* sqrt_acp_t;         /* v models: x0 = sqrt_acp_t x - sqrt_1macp_t v (ddpm3d.py:239-245) */
+    const float* sqrt_1macp_t;
+    const int32_t* step_index;       /* device counter or NULL */
+    int index;
+    int v_param;                     /* parameterization == "v" */
+    int x0_space;                    /* 1: p_c, p_u are the denoised predictions (the paper); 0: the raw outputs (diffusers) */
+    int e_nchw;                      /* as DcDdimParams; `out` has the layout of e_cond */
+    float cfg_scale;                 /* w = unconditional_guidance_scale */
+    float eta;                       /* weight of the component of the update parallel to p_c; 1 keeps plain CFG's */
+    float norm_threshold;            /* <= 0: the norm of the update is not clipped */
+    float momentum;                  /* 0: no running average (momentum_buf is then written, not read) */
+} DcApgParams;
+
+/* Per clip b, over all C*THW elements, with p_c / p_u the predictions from e_cond / e_uncond in the chosen space:
+ *   d = p_c - p_u,  m = d + momentum m_prev,  s = min(1, norm_threshold / ||m||) (1 without threshold or for m = 0),  D = s m,
+ *   par = (D . p_c / ||p_c||^2) p_c (0 for p_c = 0),  guided = p_c + (cfg_scale - 1) ((D - par) + eta par)
+ * and `out` = guided, mapped back to the model's output space when x0_space. The update kernels then take `out` as e_cond with
+ * e_uncond = NULL and cfg_scale = 1. e_cond, e_uncond: fp32 rows [B*THW, ld_e] (first C valid) or [B, C, THW] under e_nchw;
+ * out: the same layout with row stride ld_out; x, momentum_buf: fp32 [B, C, THW]; x may be NULL without x0_space.
+ * B <= 65535, ld_e >= C and ld_out >= C for rows (else DC_ERR_SHAPE); non-finite cfg_scale / eta / momentum, NaN threshold or
+ * a missing operand or table: DC_ERR_ARG. No atomics, nothing to clear between calls, capturable, bit-reproducible.
+ * replaces the plain CFG combine inside dc_ddim_step / dc_dpmpp_step (p_sample_ddim lvdm/models/samplers/ddim.py:226-245) with
+ * diffusers' AdaptiveProjectedGuidance / normalized_guidance (guiders/adaptive_projected_guidance.py), which the reference
+ * does not have.
+ *
+ * dc_apg_workspace_floats: fp32 elements of `workspace`: three partial sums per workgroup of dc_apg_reduce,
+ * 3 * B * min(256, ceil(THW / 256)); no initialisation needed (DC_ERR_ARG for a bad argument).
+ *
+ * dc_apg_reduce: momentum_buf = m in place (the caller zeroes it ahead of a run's first step), workspace[b][g][0..2] = workgroup
+ * g's sums of m*m, m*p_c, p_c*p_c. d is formed as ps (e_cond - e_uncond), ps the factor of e in p (1, -sqrt_1macp_t or
+ * -sqrt_one_minus_at / sqrt(a_t)): equal outputs give d = 0 exactly. */
+int64_t dc_apg_workspace_floats(int B, int C, int THW);
+int dc_apg_reduce(const DcApgParams* p, const float* e_cond, const float* e_uncond, int ld_e, const float* x,
+                  float* momentum_buf, int B, int C, int THW, float* workspace, void* stream);
+
+/* dc_apg_apply: adds the partial sums of dc_apg_reduce in a fixed order in float64, forms s and g = (1 - eta) s (m . p_c) /
+ * ||p_c||^2, and writes out = e_cond + (cfg_scale - 1) / ps * (s m - g p_c): one fused multiply-add on e_cond, so eta = 1
+ * without threshold and momentum is plain CFG. Same p, e_cond, x and momentum_buf as the dc_apg_reduce call before it. */
+int dc_apg_apply(const DcApgParams* p, const float* e_cond, int ld_e, const float* x, const float* momentum_buf, float* out,
+                 int ld_out, int B, int C, int THW, const float* workspace, void* stream);
+
 /* step_index[0] += 1 (device-side loop counter for the graph-captured sampler). */
 int dc_advance_counter(int32_t* counter, void* stream);
 
