@@ -10,6 +10,7 @@
 // gfx950 only (wave64).
 #include "dc_common.h"
 #include "dcrafter_hip.h"
+#include "stream_pack.h"
 
 namespace {
 
@@ -200,45 +201,15 @@ __global__ __launch_bounds__(64) void gif_lzw_kernel(const uint8_t* __restrict__
 }
 
 // ---------------------------------------------------------------------------------------------- stage 4: pack
-// exclusive prefix sum over the wave; `total` = the sum over all 64 lanes
-__device__ __forceinline__ int wave_excl_scan(int v, int lane, int& total) {
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int up = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += up;
-    }
-    total = __shfl(inc, 63, 64);
-    return inc - v;
-}
-
 // Exclusive scan of one frame's chunk bit lengths behind the 9-bit leading Clear: chunk_off[c] = the bit at which chunk c starts
 // in the frame's code stream; frame_len = data bytes + one length byte per started sub-block of 255 + the closing 00. One
-// workgroup per frame, 256 chunks per round. The entry has checked that a frame's worst case stays below 2^31 bits.
+// workgroup per frame (stream_pack.h). The entry has checked that a frame's worst case stays below 2^31 bits.
 __global__ __launch_bounds__(256) void gif_scan_kernel(const int32_t* __restrict__ chunk_bits, int32_t* __restrict__ chunk_off,
                                                        int32_t* __restrict__ frame_len, int cpf) {
-    __shared__ int part[4];
-    __shared__ int base_s;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int64_t f0 = (int64_t)blockIdx.x * cpf;
-    if (tid == 0) base_s = 9;
-    __syncthreads();
-    for (int s0 = 0; s0 < cpf; s0 += 256) {
-        const int s = s0 + tid;
-        const int v = s < cpf ? chunk_bits[f0 + s] : 0;
-        int wtot;
-        int ex = wave_excl_scan(v, lane, wtot);
-        if (lane == 0) part[wv] = wtot;
-        __syncthreads();
-        const int base = base_s;
-        for (int w = 0; w < wv; ++w) ex += part[w];
-        if (s < cpf) chunk_off[f0 + s] = base + ex;
-        __syncthreads();
-        if (tid == 0) base_s = base + part[0] + part[1] + part[2] + part[3];
-        __syncthreads();
-    }
-    if (tid == 0) {
-        const int nbytes = (base_s + 7) >> 3;
+    const int bits = frame_excl_scan(cpf, 9, chunk_off + f0, [&](int s) { return chunk_bits[f0 + s]; });
+    if (threadIdx.x == 0) {
+        const int nbytes = (bits + 7) >> 3;
         frame_len[blockIdx.x] = nbytes + (nbytes + 254) / 255 + 1;
     }
 }

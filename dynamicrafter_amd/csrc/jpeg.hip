@@ -10,6 +10,7 @@
 #include "dc_common.h"
 #include "dcrafter_hip.h"
 #include "jpeg_tables.h"
+#include "stream_pack.h"
 
 namespace {
 
@@ -120,18 +121,6 @@ constexpr HuffTables make_huff_tables() {
     return h;
 }
 __device__ const HuffTables kHuff = make_huff_tables();
-
-// exclusive prefix sum over the wave; `total` = the sum over all 64 lanes
-__device__ __forceinline__ int wave_excl_scan(int v, int lane, int& total) {
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int up = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += up;
-    }
-    total = __shfl(inc, 63, 64);
-    return inc - v;
-}
 
 // One wave per restart segment, a lane per coefficient. Per 8x8 block: a ballot of the non-zero AC coefficients gives each
 // lane its zero run (the distance to the previous non-zero lane); a lane with a non-zero coefficient builds up to three ZRL
@@ -255,30 +244,12 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const int16_t* __restr
 
 // ---------------------------------------------------------------------------------------------- stage 3: pack
 // Exclusive scan of one frame's segment lengths (each but the last followed by a 2-byte RSTm): seg_off[s] = where segment s
-// starts in the frame's scan, frame_len = the scan's length. One workgroup per frame, 256 segments per round.
+// starts in the frame's scan, frame_len = the scan's length. One workgroup per frame (stream_pack.h).
 __global__ __launch_bounds__(256) void jpeg_scan_kernel(const int32_t* __restrict__ seg_len, int32_t* __restrict__ seg_off,
                                                         int32_t* __restrict__ frame_len, int spf) {
-    __shared__ int part[4];
-    __shared__ int base_s;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int64_t f0 = (int64_t)blockIdx.x * spf;
-    if (tid == 0) base_s = 0;
-    __syncthreads();
-    for (int s0 = 0; s0 < spf; s0 += 256) {
-        const int s = s0 + tid;
-        const int v = s < spf ? seg_len[f0 + s] + (s + 1 < spf ? 2 : 0) : 0;
-        int wtot;
-        int ex = wave_excl_scan(v, lane, wtot);
-        if (lane == 0) part[wv] = wtot;
-        __syncthreads();
-        const int base = base_s;
-        for (int w = 0; w < wv; ++w) ex += part[w];
-        if (s < spf) seg_off[f0 + s] = base + ex;
-        __syncthreads();
-        if (tid == 0) base_s = base + part[0] + part[1] + part[2] + part[3];
-        __syncthreads();
-    }
-    if (tid == 0) frame_len[blockIdx.x] = base_s;
+    const int total = frame_excl_scan(spf, 0, seg_off + f0, [&](int s) { return seg_len[f0 + s] + (s + 1 < spf ? 2 : 0); });
+    if (threadIdx.x == 0) frame_len[blockIdx.x] = total;
 }
 
 // Gather: segment s of frame f -> out[f][seg_off ..], then FF D0+(s mod 8) unless it is the frame's last. Bytes that would
@@ -290,10 +261,8 @@ __global__ __launch_bounds__(256) void jpeg_gather_kernel(const uint8_t* __restr
     const int64_t seg = (int64_t)f * spf + s;
     const int len = seg_len[seg];
     const int64_t off = seg_off[seg];
-    const uint8_t* src = scratch + seg * stride;
     uint8_t* dst = out + (int64_t)f * frame_stride;
-    for (int i = threadIdx.x; i < len; i += 256)
-        if (off + i < frame_stride) dst[off + i] = src[i];
+    pack_copy_chunk(scratch + seg * stride, len, dst, off, frame_stride);
     if (threadIdx.x < 2 && s + 1 < spf && off + len + threadIdx.x < frame_stride)
         dst[off + len + threadIdx.x] = threadIdx.x == 0 ? (uint8_t)0xFF : (uint8_t)(0xD0 + (s & 7));
 }

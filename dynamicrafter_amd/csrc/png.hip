@@ -11,37 +11,11 @@
 // All integer arithmetic. gfx950 only (wave64).
 #include "dc_common.h"
 #include "dcrafter_hip.h"
+#include "stream_pack.h"
 
 namespace {
 
 constexpr int kAdlerBase = 65521;
-
-__device__ __forceinline__ int wave_sum_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int wave_max_i(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = max(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ unsigned long long wave_sum_u64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-// exclusive prefix sum over the wave; `total` = the sum over all 64 lanes
-__device__ __forceinline__ int wave_excl_scan(int v, int lane, int& total) {
-    int inc = v;
-#pragma unroll
-    for (int o = 1; o < 64; o <<= 1) {
-        const int up = __shfl_up(inc, o, 64);
-        if (lane >= o) inc += up;
-    }
-    total = __shfl(inc, 63, 64);
-    return inc - v;
-}
 
 // ---------------------------------------------------------------------------------------------- stage 1: row filters
 constexpr int kFilterMaxBlocks = 2048;          // 8 workgroups of 4 waves per CU: rows beyond that are walked by a grid stride
@@ -479,44 +453,26 @@ __global__ __launch_bounds__(256) void png_scan_kernel(const int32_t* __restrict
                                                        int32_t* __restrict__ chunk_off, uint8_t* __restrict__ out,
                                                        int32_t* __restrict__ frame_len, int N, int chunk, int cpf, int64_t stride,
                                                        int64_t frame_stride) {
-    __shared__ int part[4];
     __shared__ unsigned long long pa[4], pb[4];
-    __shared__ int base_s;
     const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
     const int64_t f0 = (int64_t)blockIdx.x * cpf;
-    if (tid == 0) base_s = 2;
-    __syncthreads();
     unsigned long long sa = 0, sb = 0;
-    for (int s0 = 0; s0 < cpf; s0 += 256) {
-        const int s = s0 + tid;
-        int v = 0;
-        if (s < cpf) {
-            v = (int)min((int64_t)max(chunk_len[f0 + s], 0), stride);
-            const uint32_t ad = chunk_adler[f0 + s];
-            const unsigned long long sc = ((ad & 0xffffu) + kAdlerBase - 1) % kAdlerBase;
-            const unsigned long long behind = (unsigned long long)(N - min((int64_t)(s + 1) * chunk, (int64_t)N));
-            sa += sc;
-            sb += ((ad >> 16) + behind * sc) % kAdlerBase;
-        }
-        int wtot;
-        int ex = wave_excl_scan(v, lane, wtot);
-        if (lane == 0) part[wv] = wtot;
-        __syncthreads();
-        const int base = base_s;
-        for (int w = 0; w < wv; ++w) ex += part[w];
-        if (s < cpf) chunk_off[f0 + s] = base + ex;
-        __syncthreads();
-        if (tid == 0) base_s = base + part[0] + part[1] + part[2] + part[3];
-        __syncthreads();
+    for (int s = tid; s < cpf; s += 256) {
+        const uint32_t ad = chunk_adler[f0 + s];
+        const unsigned long long sc = ((ad & 0xffffu) + kAdlerBase - 1) % kAdlerBase;
+        const unsigned long long behind = (unsigned long long)(N - min((int64_t)(s + 1) * chunk, (int64_t)N));
+        sa += sc;
+        sb += ((ad >> 16) + behind * sc) % kAdlerBase;
     }
     sa = wave_sum_u64(sa);
     sb = wave_sum_u64(sb);
     if (lane == 0) { pa[wv] = sa; pb[wv] = sb; }
-    __syncthreads();
+    // a chunk's length clamped to [0, stride]: what png_copy_kernel moves; the scan's barriers also publish pa / pb
+    const int end = frame_excl_scan(cpf, 2, chunk_off + f0,
+                                    [&](int s) { return (int)min((int64_t)max(chunk_len[f0 + s], 0), stride); });
     if (tid == 0) {
         const uint32_t A = (uint32_t)((1 + pa[0] + pa[1] + pa[2] + pa[3]) % kAdlerBase);
         const uint32_t B = (uint32_t)((pb[0] + pb[1] + pb[2] + pb[3]) % kAdlerBase);
-        const int end = base_s;
         uint8_t* dst = out + (int64_t)blockIdx.x * frame_stride;
         const uint8_t head[2] = {0x78, 0x01}, tail[4] = {(uint8_t)(B >> 8), (uint8_t)B, (uint8_t)(A >> 8), (uint8_t)A};
         for (int i = 0; i < 2; ++i)
@@ -534,11 +490,7 @@ __global__ __launch_bounds__(256) void png_copy_kernel(const uint8_t* __restrict
                                                        int64_t stride, int64_t frame_stride) {
     const int64_t c = (int64_t)blockIdx.y * cpf + blockIdx.x;
     const int len = (int)min((int64_t)max(chunk_len[c], 0), stride);
-    const int64_t off = chunk_off[c];
-    const uint8_t* row = scratch + c * stride;
-    uint8_t* dst = out + (int64_t)blockIdx.y * frame_stride;
-    for (int i = threadIdx.x; i < len; i += 256)
-        if (off + i < frame_stride) dst[off + i] = row[i];
+    pack_copy_chunk(scratch + c * stride, len, out + (int64_t)blockIdx.y * frame_stride, chunk_off[c], frame_stride);
 }
 
 }  // namespace

@@ -1130,17 +1130,23 @@ def jpeg_entropy(coef, scratch, seg_len, *, T, my, mx, ri, stride):
     return n_seg
 
 
+def _check_pack(name, scratch, words, out, frame_len, *, T, rows, stride, frame_stride):
+    """What the three pack wrappers share: uint8 scratch [T rows, stride] and out [T, frame_stride], int32 frame_len [T] and
+    `words` (name -> int32 tensor with one element per scratch row: the lengths, the offsets), positive geometry, T within
+    gridDim.y, and the extents the launch touches."""
+    _flat(scratch, torch.uint8, "scratch"); _flat(out, torch.uint8, "out"); _flat(frame_len, torch.int32, "frame_len")
+    if min(T, rows, stride, frame_stride) < 1 or T > 65535:
+        raise ValueError(f"{name}: T {T}, {rows} scratch rows per frame, stride {stride}, frame_stride {frame_stride}")
+    for k, t in words.items():
+        _need(_flat(t, torch.int32, k), T * rows, k)
+    _need(scratch, T * rows * stride, "scratch"); _need(out, T * frame_stride, "out"); _need(frame_len, T, "frame_len")
+
+
 def jpeg_pack(scratch, seg_len, seg_off, out, frame_len, *, T, segs_per_frame, stride, frame_stride):
     """scratch [T segs_per_frame, stride] + seg_len -> out uint8 [T, frame_stride] (RSTm between a frame's segments),
     frame_len int32 [T]; seg_off int32 [T segs_per_frame] is workspace."""
-    _flat(scratch, torch.uint8, "scratch"); _flat(out, torch.uint8, "out")
-    for t, name in ((seg_len, "seg_len"), (seg_off, "seg_off"), (frame_len, "frame_len")):
-        _flat(t, torch.int32, name)
-    if min(T, segs_per_frame, stride, frame_stride) < 1:
-        raise ValueError(f"jpeg_pack: T {T}, segs_per_frame {segs_per_frame}, stride {stride}, frame_stride {frame_stride}")
-    n_seg = T * segs_per_frame
-    _need(scratch, n_seg * stride, "scratch"); _need(seg_len, n_seg, "seg_len"); _need(seg_off, n_seg, "seg_off")
-    _need(out, T * frame_stride, "out"); _need(frame_len, T, "frame_len")
+    _check_pack("jpeg_pack", scratch, {"seg_len": seg_len, "seg_off": seg_off}, out, frame_len, T=T, rows=segs_per_frame,
+                stride=stride, frame_stride=frame_stride)
     _launch("jpeg_pack(2 kernels)", 0.0, 0.0, _hip.lib().dc_jpeg_pack, _ptr(scratch), _ptr(seg_len), _ptr(seg_off), _ptr(out),
             _ptr(frame_len), T, segs_per_frame, stride, frame_stride, stream_ptr())
     return out
@@ -1278,14 +1284,10 @@ def gif_lzw(idx, scratch, chunk_bits, *, T, hw, chunk, stride):
 def gif_pack(scratch, chunk_bits, chunk_off, out, frame_len, *, T, chunks_per_frame, stride, frame_stride):
     """scratch [T chunks_per_frame, stride] + chunk_bits -> out uint8 [T, frame_stride] (a frame's sub-blocked image data behind a
     leading Clear), frame_len int32 [T]; chunk_off int32 [T chunks_per_frame] is workspace."""
-    _flat(scratch, torch.uint8, "scratch"); _flat(out, torch.uint8, "out")
-    for t, name in ((chunk_bits, "chunk_bits"), (chunk_off, "chunk_off"), (frame_len, "frame_len")):
-        _flat(t, torch.int32, name)
-    if min(T, chunks_per_frame, stride, frame_stride) < 1 or T > 65535 or 9 + chunks_per_frame * stride * 8 > 0x7FFFFFFF:
-        raise ValueError(f"gif_pack: T {T}, chunks_per_frame {chunks_per_frame}, stride {stride}, frame_stride {frame_stride}")
-    n = T * chunks_per_frame
-    _need(scratch, n * stride, "scratch"); _need(chunk_bits, n, "chunk_bits"); _need(chunk_off, n, "chunk_off")
-    _need(out, T * frame_stride, "out"); _need(frame_len, T, "frame_len")
+    _check_pack("gif_pack", scratch, {"chunk_bits": chunk_bits, "chunk_off": chunk_off}, out, frame_len, T=T,
+                rows=chunks_per_frame, stride=stride, frame_stride=frame_stride)
+    if 9 + chunks_per_frame * stride * 8 > 0x7FFFFFFF:
+        raise ValueError(f"gif_pack: {chunks_per_frame} chunks of {stride} bytes pass 2^31 bits in a frame")
     _launch("gif_pack(2 kernels)", 0.0, 0.0, _hip.lib().dc_gif_pack, _ptr(scratch), _ptr(chunk_bits), _ptr(chunk_off), _ptr(out),
             _ptr(frame_len), T, chunks_per_frame, stride, frame_stride, stream_ptr())
     return out
@@ -1342,17 +1344,13 @@ def png_deflate(planes, scratch, chunk_len, chunk_adler, *, T, N, chunk, stride)
 def png_pack(scratch, chunk_len, chunk_adler, chunk_off, out, frame_len, *, T, N, chunk, stride, frame_stride):
     """scratch [T ceil(N / chunk), stride] + chunk_len + chunk_adler -> out uint8 [T, frame_stride] (one zlib stream per frame),
     frame_len int32 [T]; chunk_off int32 [T ceil(N / chunk)] is workspace."""
-    _flat(scratch, torch.uint8, "scratch"); _flat(out, torch.uint8, "out")
-    for t, name in ((chunk_len, "chunk_len"), (chunk_adler, "chunk_adler"), (chunk_off, "chunk_off"), (frame_len, "frame_len")):
-        _flat(t, torch.int32, name)
-    if min(T, N, chunk, stride, frame_stride) < 1 or T > 65535 or chunk > PNG_CHUNK_LIMIT:
-        raise ValueError(f"png_pack: T {T}, N {N}, chunk {chunk}, stride {stride}, frame_stride {frame_stride}")
+    if min(N, chunk) < 1 or chunk > PNG_CHUNK_LIMIT:
+        raise ValueError(f"png_pack: N {N}, chunk {chunk}")
     cpf = (N + chunk - 1) // chunk
+    _check_pack("png_pack", scratch, {"chunk_len": chunk_len, "chunk_adler": chunk_adler, "chunk_off": chunk_off}, out, frame_len,
+                T=T, rows=cpf, stride=stride, frame_stride=frame_stride)
     if 6 + cpf * stride > 0x7FFFFFFF:
         raise ValueError(f"png_pack: {cpf} chunks of {stride} bytes pass 2^31 in a frame")
-    n = T * cpf
-    _need(scratch, n * stride, "scratch"); _need(chunk_len, n, "chunk_len"); _need(chunk_adler, n, "chunk_adler")
-    _need(chunk_off, n, "chunk_off"); _need(out, T * frame_stride, "out"); _need(frame_len, T, "frame_len")
     _launch("png_pack(2 kernels)", 0.0, 0.0, _hip.lib().dc_png_pack, _ptr(scratch), _ptr(chunk_len), _ptr(chunk_adler), _ptr(chunk_off),
             _ptr(out), _ptr(frame_len), T, N, chunk, stride, frame_stride, stream_ptr())
     return out

@@ -54,6 +54,56 @@ def frames_to_uint8(video):
     return out
 
 
+# ---------------------------------------------------------------------------------------------- what the GPU encoders share
+_ENCODE_SCRATCH_BYTES = 256 << 20        # coder scratch per batch of frames (worst-case sized rows)
+
+
+def _gpu_u8_frames(name, frames, channels, hint, ndim=4):
+    """The input check of the GPU encoders: a CUDA uint8 [(t,) h, w, c] tensor with c in `channels`, returned contiguous.
+    RuntimeError for what is not on the GPU (`hint` says what there is instead), ValueError for any other dtype or shape."""
+    if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
+        raise RuntimeError(f"{name} runs on the HIP path only ({hint})")
+    if frames.dtype != torch.uint8 or frames.dim() != ndim or frames.shape[-1] not in channels:
+        want = ("t, " if ndim == 4 else "") + "h, w, " + "|".join(map(str, channels))
+        raise ValueError(f"{name}: uint8 [{want}] expected, got {frames.dtype} {tuple(frames.shape)}"
+                         + ("" if len(channels) > 1 else " (APNG takes 1 and 4 channels)"))
+    return frames.contiguous()
+
+
+def _encode_batches(name, f, stage, n_words, rows_per_frame, stride, frame_stride, bound, code, pack):
+    """The batch loop of the GPU encoders (stream_pack.h): f uint8 [t, ...] on the GPU -> t byte strings, one packed
+    stream per frame. A coder writes rows_per_frame strings per frame into scratch rows of `stride` bytes, the pack gathers them into one
+    row of frame_stride bytes per frame. Frames per batch: what _ENCODE_SCRATCH_BYTES of scratch hold, at most 65535 (a pack
+    launches one workgroup row per frame: gridDim.y). Per batch `code(frames, stage, scratch, words, n)` launches the stages in
+    front of the pack for the n frames given and `pack(scratch, words, out, frame_len, n, frame_stride)` the pack; `stage` =
+    (elements per frame, dtype) of the coder's intermediate buffer, `words` = n_words int32 buffers with one element per
+    scratch row (lengths, offsets). Then frame_len comes back, the used part of the rows in one device-to-host copy, and the
+    rows are sliced. `bound` says whether frame_stride is a proven worst case (a longer frame is an error) or a guess (the
+    pack dropped the excess and reported the full length: it runs once more into rows that wide)."""
+    t, dev = f.shape[0], f.device
+    tb = max(1, min(t, 65535, _ENCODE_SCRATCH_BYTES // (rows_per_frame * stride)))
+    stage = torch.empty(tb * stage[0], dtype=stage[1], device=dev)
+    scratch = torch.empty(tb * rows_per_frame * stride, dtype=torch.uint8, device=dev)
+    words = [torch.empty(tb * rows_per_frame, dtype=torch.int32, device=dev) for _ in range(n_words)]
+    frame_len = torch.empty(tb, dtype=torch.int32, device=dev)
+    out = torch.empty(tb * frame_stride, dtype=torch.uint8, device=dev)
+    streams = []
+    for t0 in range(0, t, tb):
+        n = min(tb, t - t0)
+        code(f[t0:t0 + n], stage, scratch, words, n)
+        pack(scratch, words, out, frame_len, n, frame_stride)
+        lens = frame_len[:n].cpu().tolist()
+        if max(lens) > frame_stride:
+            if bound:
+                raise RuntimeError(f"{name}: a frame of {max(lens)} bytes outgrew the worst case {frame_stride}")
+            frame_stride = max(lens)             # a frame outgrew the guess (the kernel dropped the excess): pack into wider rows
+            out = torch.empty(tb * frame_stride, dtype=torch.uint8, device=dev)
+            pack(scratch, words, out, frame_len, n, frame_stride)
+        host = out[:n * frame_stride].view(n, frame_stride)[:, :max(lens)].cpu().numpy()
+        streams += [host[i, :lens[i]].tobytes() for i in range(n)]
+    return streams
+
+
 # ---------------------------------------------------------------------------------------------- PNG / APNG (zlib, or csrc/png.hip)
 def _chunk(tag, data):
     return struct.pack(">I", len(data)) + tag + data + struct.pack(">I", zlib.crc32(tag + data) & 0xFFFFFFFF)
@@ -73,9 +123,6 @@ def _scanlines(frame, level):
     return zlib.compress(raw.tobytes(), level)
 
 
-_PNG_SCRATCH_BYTES = 256 << 20           # deflate scratch per batch of frames (worst-case sized rows)
-
-
 def png_deflate_mode(deflate=None):
     """"zlib" (the host compressor on filter-0 scanlines) or "hip" (csrc/png.hip); None reads the environment variable
     DC_PNG_DEFLATE and falls back to "zlib"."""
@@ -91,11 +138,7 @@ def encode_png_frames(frames_u8, chunk=None):
     payload of an IDAT / fdAT chunk each. Lossless: adaptive row filters, then every `chunk` bytes of scanlines (default
     ops.PNG_CHUNK, at most 65535) deflated on their own with run-length matches and dynamic Huffman tables, or stored where that is
     not shorter. Three launches per batch of frames and one device-to-host copy of the packed streams."""
-    if not isinstance(frames_u8, torch.Tensor) or not frames_u8.is_cuda:
-        raise RuntimeError("encode_png_frames runs on the HIP path only (deflate='zlib' is the host path)")
-    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4 or frames_u8.shape[3] not in (1, 3, 4):
-        raise ValueError(f"encode_png_frames: uint8 [t, h, w, 1|3|4] expected, got {frames_u8.dtype} {tuple(frames_u8.shape)}")
-    f = frames_u8.contiguous()
+    f = _gpu_u8_frames("encode_png_frames", frames_u8, (1, 3, 4), "deflate='zlib' is the host path")
     t, h, w, c = f.shape
     N = h * (1 + w * c)
     if t < 1 or h < 1 or w < 1 or N > 0x7FFFFFFF:
@@ -103,38 +146,23 @@ def encode_png_frames(frames_u8, chunk=None):
     chunk = ops.PNG_CHUNK if chunk is None else int(chunk)
     if not 1 <= chunk <= ops.PNG_CHUNK_LIMIT:
         raise ValueError(f"chunk must be in 1..{ops.PNG_CHUNK_LIMIT} bytes, got {chunk}")
-    dev = f.device
-    cpf = (N + chunk - 1) // chunk
     stride = ops.png_chunk_max_bytes(min(chunk, N))
-    frame_stride = ops.png_frame_max_bytes(N, chunk)
-    tb = max(1, min(t, 65535, _PNG_SCRATCH_BYTES // (cpf * stride)))     # frames per batch
-    planes = torch.empty(tb * N, dtype=torch.uint8, device=dev)
-    scratch = torch.empty(tb * cpf * stride, dtype=torch.uint8, device=dev)
-    chunk_len, chunk_adler, chunk_off = (torch.empty(tb * cpf, dtype=torch.int32, device=dev) for _ in range(3))
-    frame_len = torch.empty(tb, dtype=torch.int32, device=dev)
-    out = torch.empty(tb * frame_stride, dtype=torch.uint8, device=dev)
-    streams = []
-    for t0 in range(0, t, tb):
-        n = min(tb, t - t0)
-        ops.png_filter(f[t0:t0 + n], planes)
-        ops.png_deflate(planes, scratch, chunk_len, chunk_adler, T=n, N=N, chunk=chunk, stride=stride)
-        ops.png_pack(scratch, chunk_len, chunk_adler, chunk_off, out, frame_len, T=n, N=N, chunk=chunk, stride=stride,
-                     frame_stride=frame_stride)
-        lens = frame_len[:n].cpu().tolist()
-        if max(lens) > frame_stride:
-            raise RuntimeError(f"encode_png_frames: a frame of {max(lens)} bytes outgrew the worst case {frame_stride}")
-        host = out[:n * frame_stride].view(n, frame_stride)[:, :max(lens)].cpu().numpy()
-        streams += [host[i, :lens[i]].tobytes() for i in range(n)]
-    return streams
+
+    def code(frames, planes, scratch, words, n):
+        ops.png_filter(frames, planes)
+        ops.png_deflate(planes, scratch, words[0], words[1], T=n, N=N, chunk=chunk, stride=stride)
+
+    def pack(scratch, words, out, frame_len, n, frame_stride):
+        ops.png_pack(scratch, *words, out, frame_len, T=n, N=N, chunk=chunk, stride=stride, frame_stride=frame_stride)
+
+    return _encode_batches("encode_png_frames", f, (N, torch.uint8), 3, (N + chunk - 1) // chunk, stride,
+                           ops.png_frame_max_bytes(N, chunk), True, code, pack)
 
 
 def _hip_streams(name, frames, ndim):
     """The zlib streams of deflate="hip" for uint8 [(t,) h, w, c] on the GPU; refuses everything else before a file exists."""
-    if not isinstance(frames, torch.Tensor) or not frames.is_cuda:
-        raise RuntimeError(f"{name}: deflate='hip' needs a CUDA uint8 tensor (deflate='zlib' takes numpy and CPU tensors)")
-    if frames.dtype != torch.uint8 or frames.dim() != ndim or frames.shape[-1] not in (1, 3, 4):
-        raise ValueError(f"{name}: uint8 [{'t, ' if ndim == 4 else ''}h, w, 1|3|4] expected, got {frames.dtype} {tuple(frames.shape)}")
-    return encode_png_frames(frames if ndim == 4 else frames[None])
+    f = _gpu_u8_frames(f"{name}: deflate='hip'", frames, (1, 3, 4), "deflate='zlib' takes numpy and CPU tensors", ndim)
+    return encode_png_frames(f if ndim == 4 else f[None])
 
 
 def _png_file(w, h, c, stream):
@@ -212,7 +240,6 @@ JPEG_DHT = (
                   "6272d10a162434e125f11718191a262728292a35363738393a434445464748494a" + _AC_COMMON[0] + "82838485868788898a"
                   + _AC_COMMON[1] + "e2e3e4e5e6e7e8e9eaf2f3f4f5f6f7f8f9fa"),
 )
-_JPEG_SCRATCH_BYTES = 256 << 20          # entropy-coding scratch per batch of frames (worst-case sized rows)
 
 
 def jpeg_quant_tables(quality):
@@ -249,13 +276,7 @@ def encode_jpeg_frames(frames_u8, quality=90, restart_mcus=None):
     Baseline JPEG, YCbCr 4:2:0; `restart_mcus` = MCUs (16x16 pixels) per restart interval, i.e. per independently coded
     segment (default 8, or the whole frame if it is smaller). Three launches per batch of frames, one device-to-host copy of
     the packed scans."""
-    if not isinstance(frames_u8, torch.Tensor) or not frames_u8.is_cuda:
-        raise RuntimeError("encode_jpeg_frames runs on the HIP path only (there is no CPU fallback)")
-    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4:
-        raise ValueError(f"encode_jpeg_frames: uint8 [t, h, w, 3] expected, got {frames_u8.dtype} {tuple(frames_u8.shape)}")
-    if frames_u8.shape[3] != 3:
-        raise ValueError(f"encode_jpeg_frames: 3 channels expected, got {frames_u8.shape[3]} (APNG takes 1 and 4)")
-    f = frames_u8.contiguous()
+    f = _gpu_u8_frames("encode_jpeg_frames", frames_u8, (3,), "there is no CPU fallback")
     t, h, w, _ = f.shape
     if t < 1 or not (1 <= h <= 65535 and 1 <= w <= 65535):
         raise ValueError(f"encode_jpeg_frames: frames of {h} x {w} x {t}")
@@ -266,32 +287,21 @@ def encode_jpeg_frames(frames_u8, quality=90, restart_mcus=None):
         raise ValueError(f"restart_mcus must be in 1..65535, got {restart_mcus}")
     _, qz = jpeg_quant_tables(quality)
     header = jpeg_header(w, h, qz, ri)
-    dev = f.device
-    qtab = torch.from_numpy(qz).to(dev)
+    qtab = torch.from_numpy(qz).to(f.device)
     spf = (nmcu + ri - 1) // ri
     stride = min(ri, nmcu) * ops.JPEG_MCU_MAX_BYTES + 1
-    tb = max(1, min(t, _JPEG_SCRATCH_BYTES // (spf * stride)))            # frames per batch
-    coef = torch.empty(tb * nmcu * 384, dtype=torch.int16, device=dev)
-    scratch = torch.empty(tb * spf * stride, dtype=torch.uint8, device=dev)
-    seg_len, seg_off = (torch.empty(tb * spf, dtype=torch.int32, device=dev) for _ in range(2))
-    frame_len = torch.empty(tb, dtype=torch.int32, device=dev)
-    frame_stride = nmcu * 384 + 2 * spf          # 1.5 bytes per pixel: a first guess far above typical frames, not a bound
-    out = torch.empty(tb * frame_stride, dtype=torch.uint8, device=dev)
-    files = []
-    for t0 in range(0, t, tb):
-        n = min(tb, t - t0)
-        ops.jpeg_dct_quant(f[t0:t0 + n], qtab, coef)
-        ops.jpeg_entropy(coef, scratch, seg_len, T=n, my=my, mx=mx, ri=ri, stride=stride)
-        ops.jpeg_pack(scratch, seg_len, seg_off, out, frame_len, T=n, segs_per_frame=spf, stride=stride, frame_stride=frame_stride)
-        lens = frame_len[:n].cpu().tolist()
-        if max(lens) > frame_stride:             # a frame outgrew the guess (the kernel dropped the excess): pack into wider rows
-            frame_stride = max(lens)
-            out = torch.empty(tb * frame_stride, dtype=torch.uint8, device=dev)
-            ops.jpeg_pack(scratch, seg_len, seg_off, out, frame_len, T=n, segs_per_frame=spf, stride=stride,
-                          frame_stride=frame_stride)
-        host = out[:n * frame_stride].view(n, frame_stride)[:, :max(lens)].cpu().numpy()
-        files += [header + host[i, :lens[i]].tobytes() + b"\xff\xd9" for i in range(n)]
-    return files
+
+    def code(frames, coef, scratch, words, n):
+        ops.jpeg_dct_quant(frames, qtab, coef)
+        ops.jpeg_entropy(coef, scratch, words[0], T=n, my=my, mx=mx, ri=ri, stride=stride)
+
+    def pack(scratch, words, out, frame_len, n, frame_stride):
+        ops.jpeg_pack(scratch, *words, out, frame_len, T=n, segs_per_frame=spf, stride=stride, frame_stride=frame_stride)
+
+    # rows of 1.5 bytes per pixel: a first guess far above typical frames, not a bound
+    scans = _encode_batches("encode_jpeg_frames", f, (nmcu * 384, torch.int16), 2, spf, stride, nmcu * 384 + 2 * spf, False,
+                            code, pack)
+    return [header + scan + b"\xff\xd9" for scan in scans]
 
 
 def write_jpeg(path, frame_u8, quality=90):
@@ -345,9 +355,6 @@ def write_avi_mjpeg(path, jpeg_frames, width, height, fps):
 
 
 # ---------------------------------------------------------------------------------------------- animated GIF
-_GIF_SCRATCH_BYTES = 256 << 20           # LZW scratch per batch of frames (worst-case sized rows)
-
-
 def gif_palette(hist):
     """hist: 32768 pixel counts over the bins (r>>3)<<10 | (g>>3)<<5 | (b>>3) (numpy or tensor, int32 bit patterns are read as
     uint32) -> palette uint8 [n <= 256, 3]. A deterministic box-splitting quantiser on the occupied cells of the 32^3 grid with
@@ -435,13 +442,7 @@ def encode_gif_frames(frames_u8, dither=0, chunk=None):
     nearest-colour search; 0 = none: the smallest file, smooth gradients band. `chunk` = pixels per independently LZW-coded chunk
     (default ops.GIF_CHUNK). One histogram launch and one device-to-host copy of 128 KiB for the palette, then three launches per
     batch of frames and one copy of the packed data."""
-    if not isinstance(frames_u8, torch.Tensor) or not frames_u8.is_cuda:
-        raise RuntimeError("encode_gif_frames runs on the HIP path only (there is no CPU fallback)")
-    if frames_u8.dtype != torch.uint8 or frames_u8.dim() != 4:
-        raise ValueError(f"encode_gif_frames: uint8 [t, h, w, 3] expected, got {frames_u8.dtype} {tuple(frames_u8.shape)}")
-    if frames_u8.shape[3] != 3:
-        raise ValueError(f"encode_gif_frames: 3 channels expected, got {frames_u8.shape[3]} (APNG takes 1 and 4)")
-    f = frames_u8.contiguous()
+    f = _gpu_u8_frames("encode_gif_frames", frames_u8, (3,), "there is no CPU fallback")
     t, h, w, _ = f.shape
     if t < 1 or not (1 <= h <= 65535 and 1 <= w <= 65535):
         raise ValueError(f"encode_gif_frames: frames of {h} x {w} x {t}")
@@ -451,33 +452,22 @@ def encode_gif_frames(frames_u8, dither=0, chunk=None):
     chunk = ops.GIF_CHUNK if chunk is None else int(chunk)
     if chunk < 1:
         raise ValueError(f"chunk must be at least 1 pixel, got {chunk}")
-    dev = f.device
-    hist = torch.empty(ops.GIF_HIST_BINS, dtype=torch.int32, device=dev)
+    hist = torch.empty(ops.GIF_HIST_BINS, dtype=torch.int32, device=f.device)
     ops.gif_histogram(f, hist)
     palette = gif_palette(hist)
-    pal_dev = torch.from_numpy(palette).to(dev)
+    pal_dev = torch.from_numpy(palette).to(f.device)
     cpf = (hw + chunk - 1) // chunk
     stride = ops.gif_chunk_max_bytes(min(chunk, hw))
-    frame_stride = ops.gif_frame_max_bytes(hw, chunk)
-    tb = max(1, min(t, _GIF_SCRATCH_BYTES // (cpf * stride)))             # frames per batch
-    idx = torch.empty(tb * hw, dtype=torch.uint8, device=dev)
-    scratch = torch.empty(tb * cpf * stride, dtype=torch.uint8, device=dev)
-    chunk_bits, chunk_off = (torch.empty(tb * cpf, dtype=torch.int32, device=dev) for _ in range(2))
-    frame_len = torch.empty(tb, dtype=torch.int32, device=dev)
-    out = torch.empty(tb * frame_stride, dtype=torch.uint8, device=dev)
-    images = []
-    for t0 in range(0, t, tb):
-        n = min(tb, t - t0)
-        ops.gif_map(f[t0:t0 + n], pal_dev, idx, n=palette.shape[0], dither=int(dither))
-        ops.gif_lzw(idx, scratch, chunk_bits, T=n, hw=hw, chunk=chunk, stride=stride)
-        ops.gif_pack(scratch, chunk_bits, chunk_off, out, frame_len, T=n, chunks_per_frame=cpf, stride=stride,
-                     frame_stride=frame_stride)
-        lens = frame_len[:n].cpu().tolist()
-        if max(lens) > frame_stride:
-            raise RuntimeError(f"encode_gif_frames: a frame of {max(lens)} bytes outgrew the worst case {frame_stride}")
-        host = out[:n * frame_stride].view(n, frame_stride)[:, :max(lens)].cpu().numpy()
-        images += [host[i, :lens[i]].tobytes() for i in range(n)]
-    return palette, images
+
+    def code(frames, idx, scratch, words, n):
+        ops.gif_map(frames, pal_dev, idx, n=palette.shape[0], dither=int(dither))
+        ops.gif_lzw(idx, scratch, words[0], T=n, hw=hw, chunk=chunk, stride=stride)
+
+    def pack(scratch, words, out, frame_len, n, frame_stride):
+        ops.gif_pack(scratch, *words, out, frame_len, T=n, chunks_per_frame=cpf, stride=stride, frame_stride=frame_stride)
+
+    return palette, _encode_batches("encode_gif_frames", f, (hw, torch.uint8), 2, cpf, stride,
+                                    ops.gif_frame_max_bytes(hw, chunk), True, code, pack)
 
 
 def write_gif(path, frames_u8, fps=8, loops=0, dither=0, chunk=None):

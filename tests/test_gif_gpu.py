@@ -297,6 +297,21 @@ def test_write_gif_end_to_end(tmp_path, dither):
     _check_file(S.write_gif(str(tmp_path / "d.gif"), _dev(one), fps=100), one, 100)
 
 
+def test_more_than_65535_frames_in_one_call():
+    """A pack launch takes at most 65535 frames (gridDim.y): 65537 frames of 1x1 pixels, two flat colours alternating with the
+    parity of the frame, come back as 65537 images, the same on both sides of the batch boundary. Two occupied histogram cells
+    get their centres 8 (v >> 3) + 4 as palette entries: a decoded channel is at most 4 from the frame's."""
+    from dynamicrafter_amd.utils import save_video as S
+    colours = np.array([[200, 30, 90], [20, 180, 240]], dtype=np.uint8)
+    f = colours[np.arange(65537) % 2].reshape(65537, 1, 1, 3)
+    pal, images = S.encode_gif_frames(_dev(f))
+    assert len(images) == 65537
+    assert images[65534:] == [images[0], images[1], images[0]] and images[0] != images[1]
+    d = G.decode(S.gif_file(1, 1, pal, images[:2]))
+    got = d["palette"][d["frames"]].astype(np.int32)                       # [2, 1, 1, 3]
+    assert got.shape == (2, 1, 1, 3) and np.abs(got - f[:2].astype(np.int32)).max() <= 4
+
+
 def test_encoder_refuses_what_it_cannot_code():
     from dynamicrafter_amd.utils import save_video as S
     z = lambda c: torch.zeros(1, 16, 16, c, dtype=torch.uint8, device=DEV)

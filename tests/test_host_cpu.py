@@ -170,6 +170,26 @@ def test_attn_parts_are_spelled_once():
     assert len(re.findall(r"\b192\b", src["attn_parts.h"])) == 1
 
 
+def test_pack_parts_are_spelled_once():
+    """One spelling of the pack stage of the JPEG, GIF and PNG encoders (csrc/stream_pack.h): the wave prefix sum and the
+    per-frame scan with its running base live there and the three kernel files include it; the integer wave reductions live
+    in csrc/dc_common.h beside the float ones."""
+    def code(path):
+        text = open(path).read()
+        return re.sub(r"//[^\n]*", "", re.sub(r"/\*.*?\*/", "", text, flags=re.S))
+    files = sorted(f for f in os.listdir(CSRC) if f.endswith((".hip", ".h")))
+    assert "stream_pack.h" in files and "dc_common.h" in files and len(files) > 10
+    src = {f: code(os.path.join(CSRC, f)) for f in files}
+    users = lambda text: [f for f in files if text in src[f]]
+    assert users("if (lane >= o) inc += up") == ["stream_pack.h"]                           # the wave prefix-sum step
+    assert users("part[0] + part[1] + part[2] + part[3]") == ["stream_pack.h"]              # the frame scan's running base
+    for name in ("wave_sum_i", "wave_max_i", "wave_sum_u64"):
+        definers = [f for f in files if re.search(r"__device__[^;{()]*\b" + name + r"\s*\(", src[f])]
+        assert definers == ["dc_common.h"], (name, definers)
+    for f in ("jpeg.hip", "gif.hip", "png.hip"):
+        assert '#include "stream_pack.h"' in src[f], f
+
+
 def _tiny_model(config_name, extra=None):
     from dynamicrafter_amd.utils.utils import instantiate_from_config
     from tests.golden_cfg import TINY_AE, TINY_UNET

@@ -171,6 +171,22 @@ def test_entropy_bit_exact_on_corner_cases(name, ri):
         print(f"longest codes, ri {ri}: longest segment {sl.max()} bytes of stride {stride}")
 
 
+def test_pack_scans_more_than_256_segments_per_frame():
+    """261 MCUs in a row at ri = 1: 261 segments per frame, so the frame scan of the pack takes a second round, of 5 segments (a
+    partial wave), on top of the running base of the first 256. A random DC in every block and five random ACs at random
+    places make the segments differ in length."""
+    rng = np.random.default_rng(1)
+    coef = np.zeros((2, 1, 261, 6, 64), dtype=np.int16)
+    coef[..., 0] = rng.integers(-1024, 1017, size=coef.shape[:-1])
+    np.put_along_axis(coef, rng.integers(1, 64, size=coef.shape[:-1] + (5,)),
+                      rng.integers(-1023, 1024, size=coef.shape[:-1] + (5,)).astype(np.int16), axis=-1)
+    sl, _ = _check_entropy(coef, 1)                              # every segment and the packed scan against the restatement
+    sl = sl.reshape(2, 261)
+    for t in range(2):
+        print(f"frame {t}: segment lengths {sl[t].min()}..{sl[t].max()} bytes, {np.unique(sl[t]).size} distinct")
+        assert np.unique(sl[t, :256]).size > 1 and np.unique(sl[t, 256:]).size > 1
+
+
 def test_pack_drops_what_does_not_fit_and_reports_the_full_length():
     """frame_stride below a frame's length: nothing is written past the row, frame_len still tells the full length."""
     coef = _synthetic("random")
@@ -215,6 +231,28 @@ def test_encode_jpeg_frames_end_to_end(kind, hw, restart_mcus):
             ours, ref = J.psnr(np.asarray(im), f[t]), _pillow_psnr(f[t], q)
             print(f"{kind} {H}x{W} q{q} frame {t}: {ours:.3f} dB, Pillow's encoder {ref:.3f} dB, {len(data)} bytes")
             assert ours >= ref - PSNR_MARGIN_DB
+
+
+def test_more_than_65535_frames_in_one_call():
+    """A pack launch takes at most 65535 frames (gridDim.y): 65537 frames of 1x1 pixels, two flat colours alternating with the
+    parity of the frame, come back as 65537 files, the same on both sides of the batch boundary.
+    The loss of a flat frame at quality 90: its only coefficients are the three DCs, 8 x the sample, quantised in steps of 3
+    (both tables: (16 * 20 + 50) // 100 = (17 * 20 + 50) // 100 = 3), so Y, Cb and Cr come back within 1.5 / 8 and are rounded
+    to integers by the decoder: 0.6875 each at most. Through the inverse colour transform that is 0.6875 * (1 + 1.402) = 1.65
+    in R, 0.6875 * (1 + 0.344 + 0.714) = 1.42 in G and 0.6875 * (1 + 1.772) = 1.91 in B, and one more rounding (0.5): no
+    channel of the decoded pixel is more than 2 from the frame's."""
+    from dynamicrafter_amd.utils import save_video as S
+    colours = np.array([[200, 30, 90], [20, 180, 240]], dtype=np.uint8)
+    f = colours[np.arange(65537) % 2].reshape(65537, 1, 1, 3)
+    files = S.encode_jpeg_frames(torch.from_numpy(f).to(DEV), quality=90)
+    assert len(files) == 65537
+    assert files[65534:] == [files[0], files[1], files[0]] and files[0] != files[1]
+    for t in range(2):
+        im = _decode(files[t])
+        assert im.size == (1, 1) and im.mode == "RGB"
+        d = np.abs(np.asarray(im).astype(np.int32) - f[t].astype(np.int32))
+        print(f"frame {t}: {f[t].ravel().tolist()} decodes to {np.asarray(im).ravel().tolist()}")
+        assert d.max() <= 2
 
 
 def test_encoder_refuses_what_it_cannot_code(tmp_path):
