@@ -89,6 +89,8 @@ class DcSdsParams(C.Structure):
 _P, _I, _F, _L = C.c_void_p, C.c_int, C.c_float, C.c_int64
 SIGNATURES = {
     "dc_gemm_conv": (_I, [C.POINTER(DcGemmParams), _P]),
+    "dc_gemm_fit": (_I, [C.POINTER(DcGemmParams), _P]),
+    "dc_gemm_fit_shape": (_I, [_I, _I, _I]),
     "dc_gemm_workspace_bytes": (_L, []),
     "dc_gemm_last_variant": (C.c_char_p, []),
     "dc_gemm_set_plan": (_I, [_I]),

@@ -32,6 +32,34 @@ _TA_FUSED = os.environ.get("DC_TA_FUSED", "1") != "0"
 _TA_FUSED_C = tuple(int(k) for k in os.environ.get("DC_TA_FUSED_C", "320,640").split(","))      # widths of the fused temporal attention
 _FFP_FUSED = os.environ.get("DC_FFP_FUSED", "1") != "0"
 _TC_FUSED = os.environ.get("DC_TC_FUSED", "1") != "0"
+# The exact-fit GEMM (csrc/gemm_fit.hip) takes a plain Linear / 1x1 conv where its output is a whole number of rounds of 288 x 320
+# tiles over the CUs (ops.gemm_fits: at the native 1024 resolution the level-2 rows, 18432, and the level-1 rows, 73728) AND the
+# weight shape (N, K) is listed in _FIT_ROUTES. Two conditions put a shape on the list (tools/fit_ab.py, profiles/fit_ab.json):
+# the per-launch A/B against what ops.gemm launches is a win (the new kernel's median below the other kernel's fastest run), and
+# the new kernel returns the bits of the kernel it replaces, so that a step computes what it computed before. DC_GEMM_FIT=0: ops.gemm everywhere.
+_GEMM_FIT = os.environ.get("DC_GEMM_FIT", "1") != "0"
+_FIT_ROUTES = {
+    # (N, K): us per launch at M = 18432 on 256 CUs, exact-fit median / ops.gemm fastest run [its kernel]; bits
+    (1280, 1280): "61 / 86 [gemm_persist_kernel<128>]; with residual 79 / 95; same bits",     # proj_in, to_q, to_out, proj_out of level 2
+    (3840, 1280): "168 / 207 [gemm_persist_kernel<320>]; same bits",     # level-2 qkv
+}
+# Measured and NOT routed: faster per launch, but ops.gemm runs these on the one-wave kernel with 32 of its 288 tiles cut along K
+# (fp32 partials summed in another order) and, with a residual, rounds twice where the exact-fit kernel rounds once. The outputs
+# differ in the last bit of a few elements per million (rel-L2 9e-6 per launch) and a UNet forward moves by rel-L2 9e-3 on
+# seeded weights (tests/test_gemm_fit_gpu.py measures both): a changed result, so they stay on ops.gemm.
+_FIT_MEASURED_NOT_ROUTED = {
+    (1280, 5120): "213 / 255 [gemm_pipe320x16_kernel+splitk]",     # level-2 ff2 (+ residual)
+    (640, 2560): "251 / 316 [gemm_pipe320x16_kernel+splitk]",      # level-1 ff2 (+ residual), M = 73728
+    (1280, 1920): "78 / 123 [gemm_pipe320x16_kernel+splitk]",     # 1x1 skips of the up path
+    (1280, 2560): "100 / 143 [gemm_pipe320x16_kernel+splitk]",
+}
+
+
+def _linear(a, pw, out, residual=None):
+    """out = a @ W^T + b (+ residual): the exact-fit kernel where the shape is one of its routes, else the dc_gemm_conv dispatch"""
+    if _GEMM_FIT and (pw.N, pw.K) in _FIT_ROUTES and ops.gemm_fits(out.shape[0], pw):
+        return ops.gemm_fit(a, pw, out, residual=residual)
+    return ops.gemm(a, pw, out, residual=residual)
 # below this row count the tile GEMMs + norm kernels are used (the 1024 config's level-0/1 tensors have >= 73728 rows; at the
 # 512 / 256 configs level 1 has 20480 / 8192: fused kernels measured 42.1 -> 41.8 and 24.1 -> 23.4 ms per step there)
 _FUSED_MIN_ROWS = int(os.environ.get("DC_FUSED_MIN_ROWS", "4096"))
@@ -447,7 +475,7 @@ class UNetModel(nn.Module):
         h = self._gn(h1, W["gn2"], "gn", n_inst=g["F"], rpi=g["HW"], eps=1e-5, silu=True)
         skip = x
         if "skip" in W:
-            skip = ops.gemm(x, W["skip"], A.get("res_skip", M, cout, device=dev))
+            skip = _linear(x, W["skip"], A.get("res_skip", M, cout, device=dev))
         has_tc = "tc" in W
         final = (lambda: out if out is not None else A.get(out_tag, M, cout, device=dev))
         h2 = ops.gemm(h, W["conv2"], A.get("res_h2", M, cout, device=dev) if has_tc else final(), conv=conv,
@@ -477,14 +505,14 @@ class UNetModel(nn.Module):
         normalised copy never reaches HBM), otherwise LayerNorm kernel + GEMM."""
         if _LN_FUSED and pw.K in _LN_FUSED_K and pw.N % 32 == 0 and h.shape[0] >= _FUSED_MIN_ROWS:
             return ops.ln_linear(h, pw, out, ln=ln, ln_eps=1e-5)
-        return ops.gemm(self._ln(h, ln, "ln"), pw, out)
+        return _linear(self._ln(h, ln, "ln"), pw, out)
 
     def _lin_res(self, x, pw, res, out):
         """out = res + Linear(x) (attention out-projections, proj_out): at dim 320 / 640 and level-0 / level-1 row counts the
         X-stationary kernel (HBM-bound on x + res + out), otherwise the tile GEMM with the residual through its LDS ring."""
         if _LR_FUSED and pw.K in _LN_FUSED_K and pw.N % 32 == 0 and x.shape[0] >= _FUSED_MIN_ROWS:
             return ops.linear_residual(x, pw, res, out)
-        return ops.gemm(x, pw, out, residual=res)
+        return _linear(x, pw, out, residual=res)
 
     def _gn_linear(self, x, gnw, pw, out, *, n_inst, rpi):
         """Linear(GroupNorm(x)) (eps 1e-6, no activation: the transformers' norm -> proj_in): at dim 320 / 640 and level-0 / level-1
@@ -493,7 +521,7 @@ class UNetModel(nn.Module):
             st = self._arena.get("gn_stats", n_inst * 32 * 2, 1, torch.float32, x.device)
             ops.groupnorm_stats(x, st, groups=32, n_inst=n_inst, rows_per_inst=rpi, eps=1e-6)
             return ops.gn_linear(x, gnw[0], gnw[1], st, pw, out, groups=32, rows_per_inst=rpi)
-        return ops.gemm(self._gn(x, gnw, "gn", n_inst=n_inst, rpi=rpi, eps=1e-6, silu=False), pw, out)
+        return _linear(self._gn(x, gnw, "gn", n_inst=n_inst, rpi=rpi, eps=1e-6, silu=False), pw, out)
 
     def _attn_self_spatial(self, Wa, ln, h, g, heads):
         A = self._arena
@@ -524,7 +552,7 @@ class UNetModel(nn.Module):
             return ops.ff_geglu_fused320(h, Wb["ff1"], Wb["ff2p"], Wb["ff2"].bias, h, residual=h, ln=Wb["norm3"], ln_eps=1e-5)
         n = self._ln(h, Wb["norm3"], tag)
         mid = ops.gemm(n, Wb["ff1"], A.get("ffmid", h.shape[0], Wb["ff1"].N // 2, device=h.device), geglu=True)
-        return ops.gemm(mid, Wb["ff2"], h, residual=h)
+        return _linear(mid, Wb["ff2"], h, residual=h)
 
     def _ff_proj(self, W, h, x, out):
         """the tail of a transformer: h = h + ff(norm3(h)); return x + proj_out(h) - one kernel at dim 320 / level-0 rows"""

@@ -240,6 +240,38 @@ def gemm(a, pw, out, *, M=None, residual=None, rowvec=None, rows_per_vec=1, gegl
     return out
 
 
+def gemm_fits(M, pw):
+    """Does out[M, pw.N] = a @ pw.w.T tile exactly into rounds of 288 x 320 tiles over this device's CUs (dc_gemm_fit_shape)?
+    Shape only: gemm_fit itself still checks strides and alignment."""
+    return bool(_hip.lib().dc_gemm_fit_shape(int(M), int(pw.N), int(pw.K)))
+
+
+def gemm_fit(a, pw, out, residual=None):
+    """out[M, N] = a @ pw.w[:N].T (+ pw.bias) (+ residual) on the exact-fit kernel (gemm_fit.hip); M = out.shape[0]. bf16 rows;
+    bias and residual are added in fp32 and rounded once; `out` may be `residual`. Raises where the shape does not fit
+    (gemm_fits): there is no second path behind it."""
+    _rows(a, "a")
+    _rows(out, "out")
+    M = out.shape[0]
+    if a.shape[0] < M or a.shape[1] < pw.K or out.shape[1] < pw.N or pw.taps != 1:
+        raise ValueError(f"gemm_fit: a {tuple(a.shape)} / out {tuple(out.shape)} do not match the weight [N={pw.N}, K={pw.K}]")
+    if residual is not None and (_rows(residual, "residual").shape[0] < M or residual.shape[1] < pw.N):
+        raise ValueError(f"gemm_fit: residual {tuple(residual.shape)} does not cover [{M}, {pw.N}]")
+    p = DcGemmParams()
+    p.A, p.W, p.C = a.data_ptr(), pw.w.data_ptr(), out.data_ptr()
+    p.bias = 0 if pw.bias is None else pw.bias.data_ptr()
+    p.residual = 0 if residual is None else residual.data_ptr()
+    p.ldr = 0 if residual is None else residual.stride(0)
+    p.lda, p.ldc = a.stride(0), out.stride(0)
+    p.M, p.N, p.K, p.n_pad = M, pw.N, pw.K, pw.n_pad
+    p.Cin, p.mode, p.flags, p.alpha = pw.Cin, 0, 0, 1.0
+    k_real = pw.k_real if pw.k_real else pw.K
+    nbytes = 2.0 * M * k_real + 2.0 * pw.N * pw.K + 2.0 * M * pw.N * (2 if residual is not None else 1)
+    _launch("gemm_fit_kernel", 2.0 * M * pw.N * k_real, nbytes, _hip.lib().dc_gemm_fit, C.byref(p), stream_ptr(),
+            tag=(0, M, pw.N, k_real))
+    return out
+
+
 _gemm_ws = {}
 
 

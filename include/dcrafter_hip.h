@@ -83,6 +83,19 @@ int64_t dc_gemm_workspace_bytes(void);
  *           GEGLU      lvdm/modules/attention.py:415-422 (DC_GEMM_GEGLU) */
 int dc_gemm_conv(const DcGemmParams* p, void* stream);
 
+/* The exact-fit GEMM (gemm_fit.hip): C[M,N] = A[M,K] W[N,K]^T (+ bias) (+ bf16 residual), bf16 output, fp32 accumulation, in
+ * 288 x 320 output tiles, one workgroup per CU, for launches whose (M / 288) (N / 320) tiles are a whole number of rounds over
+ * the device's CUs (queried at run time): no ragged last round, no split-K. Operands as dc_gemm_conv takes them in mode 0 (lda /
+ * ldc / ldr row strides, W bf16 [n_pad][K]); bias and residual are added in fp32 and the sum is rounded once; C may be the
+ * residual. Refuses, before any launch, with DC_ERR_ARG: mode != 0, fp32 output, GEGLU, GELU, a row vector, alpha != 1, a null
+ * operand, no usable device; with DC_ERR_SHAPE: M % 288, N % 320 or K % 64 != 0, a tile count that is no multiple of the CU count,
+ * row strides that are no multiple of 8 elements, or operands that are not 16-byte aligned.
+ * dc_gemm_fit_shape answers 1 when [M x N x K] passes the shape rules on the current device, else 0, and launches nothing.
+ * replaces: nn.Linear lvdm/modules/attention.py:53-57,75-76,269,290,336,362,438 and the 1x1 nn.Conv2d skip_connection
+ *           lvdm/modules/networks/openaimodel3d.py:187 at the UNet's native resolution */
+int dc_gemm_fit(const DcGemmParams* p, void* stream);
+int dc_gemm_fit_shape(int M, int N, int K);
+
 /* GroupNorm (+ optional SiLU) over channels-last rows; statistics in fp32.
  * One "instance" = rows_per_inst consecutive rows sharing statistics: H*W for the 4-D norms, T*H*W for the 5-D
  * norms of TemporalConvBlock / TemporalTransformer.
