@@ -97,6 +97,7 @@ SIGNATURES = {
     "dc_groupnorm": (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _F, _I, _P, _P]),
     "dc_groupnorm_workspace_bytes": (_L, [_I, _I, _I]),
     "dc_layernorm": (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _F, _P]),
+    "dc_ln_pool_tokens": (_I, [_P, _I, _P, _I, _P, _P, _I, _I, _I, _I, _I, _I, _F, _P]),
     "dc_flash_attn_d64": (_I, [_P, _P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _I, _L, _L, _F, _I, _F, _P]),
     "dc_ff_geglu_fused320": (_I, [_P, _I, _P, _P, _F, _P, _P, _P, _P, _P, _I, _P, _I, _I, _P]),
     "dc_ff_geglu_proj_fused320": (_I, [_P, _I, _P, _P, _F, _P, _P, _P, _P, _P, _P, _P, _I, _P, _I, _I, _P]),

@@ -28,6 +28,10 @@ behaves as the reference's, including the 3-branch guidance of ddim_multiplecond
     (ops.apg_guide) between the UNet and the unchanged update, which then takes the guided output as its only branch; the
     running update lives in the run and is zeroed by rewind(). Two branches only, not with guidance_rescale (check_apg,
     DESIGN 4.13). None (default): nothing is added.
+  * `token_downsampling=dict(factor=2, levels=(0,), mode="nearest")` (not in the reference) on `sample`, `ddim_sampling`,
+    `decode` and `encode` runs that call with K/V token downsampling in the spatial self-attentions of the selected levels
+    (UNetModel.enable_token_downsampling) and puts the model's previous setting back afterwards, also when
+    the call raises; None (default) leaves the model's setting as it is.
 """
 import contextlib
 import functools
@@ -92,6 +96,42 @@ def _takes_freeu(fn):
     @functools.wraps(fn)
     def wrapped(self, *args, freeu=None, **kwargs):
         with freeu_scope(self.model, freeu):
+            return fn(self, *args, **kwargs)
+    return wrapped
+
+
+TOKEN_DS_KEYS = ("factor", "levels", "mode")
+
+
+@contextlib.contextmanager
+def token_downsampling_scope(model, cfg):
+    """Run a block with K/V token downsampling `cfg` (enable_token_downsampling's arguments as a dict: factor, levels, mode)
+    on the UNet of `model` (a LatentDiffusion: its model.diffusion_model, or a UNetModel itself) and restore the setting that
+    was in force before, whatever happens inside. None changes nothing. A run captured inside the block keeps the setting in
+    its graph after the block ends."""
+    if cfg is None:
+        yield
+        return
+    if not isinstance(cfg, dict):
+        raise ValueError(f"token_downsampling= takes a dict with keys {list(TOKEN_DS_KEYS)} or None, got {type(cfg).__name__}")
+    unknown = sorted(set(cfg) - set(TOKEN_DS_KEYS))
+    if unknown:
+        raise ValueError(f"token_downsampling=: unknown keys {unknown}; known: {list(TOKEN_DS_KEYS)}")
+    net = getattr(getattr(model, "model", None), "diffusion_model", model)
+    if not hasattr(net, "set_token_downsampling"):
+        raise ValueError(f"token_downsampling=: {type(net).__name__} has no token downsampling (expected the HIP UNetModel)")
+    prev = net.set_token_downsampling(dict(cfg))          # validates before anything runs
+    try:
+        yield
+    finally:
+        net.set_token_downsampling(prev)
+
+
+def _takes_token_downsampling(fn):
+    """Gives a sampler method the keyword `token_downsampling=` (token_downsampling_scope around the whole call)."""
+    @functools.wraps(fn)
+    def wrapped(self, *args, token_downsampling=None, **kwargs):
+        with token_downsampling_scope(self.model, token_downsampling):
             return fn(self, *args, **kwargs)
     return wrapped
 
@@ -547,6 +587,7 @@ class DDIMSampler(object):
         subset_end = int(min(timesteps / S, 1) * S) - 1
         return len(range(S)[:subset_end])
 
+    @_takes_token_downsampling
     @_takes_freeu
     def _denoise(self, n, cond, shape, x_T=None, callback=None, mask=None, x0=None, img_callback=None, log_every_t=100,
                  temperature=1., unconditional_guidance_scale=1., unconditional_conditioning=None, fs=None,
@@ -705,7 +746,8 @@ class DDIMSampler(object):
     def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
                use_original_steps=False, callback=None, *, fs=None, guidance_rescale=0.0, cfg_img=None,
                unconditional_conditioning_img_nonetext=None, noises=None, temperature=1., mask=None, x0=None,
-               q_noises=None, use_graph=False, img_callback=None, log_every_t=100, freeu=None, apg=None):
+               q_noises=None, use_graph=False, img_callback=None, log_every_t=100, freeu=None, apg=None,
+               token_downsampling=None):
         """ddim.py:281-301: run the last t_start DDIM steps from x_latent (at level ddim_alphas[t_start - 1]) and return
         the result. The steps are those of `sample`, on the same path (a partial FusedRun when the model has the batched
         entry), so the keyword-only options mean what they mean there; `noises` / `q_noises` are [t_start, ...], indexed
@@ -725,10 +767,11 @@ class DDIMSampler(object):
                                  unconditional_guidance_scale=unconditional_guidance_scale,
                                  unconditional_conditioning=unconditional_conditioning, fs=fs,
                                  guidance_rescale=guidance_rescale, noises=noises, use_graph=use_graph, freeu=freeu, apg=apg,
-                                 **kw)
+                                 token_downsampling=token_downsampling, **kw)
         return x_dec
 
     @torch.no_grad()
+    @_takes_token_downsampling
     @_takes_freeu
     def encode(self, x0, c, t_enc, use_original_steps=False, return_intermediates=None,
                unconditional_guidance_scale=1.0, unconditional_conditioning=None, callback=None, *, fs=None,

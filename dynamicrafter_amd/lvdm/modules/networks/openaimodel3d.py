@@ -233,6 +233,22 @@ def freeu_stages(plan, model_channels):
     return [1 if ch == 4 * model_channels else 2 if ch == 2 * model_channels else None for ch, _ in plan]
 
 
+def spatial_levels(layout):
+    """The resolution levels of a _block_layout that hold a SpatialTransformer (level 0 = the latent's own resolution, one more
+    per downsampling block), as a sorted list."""
+    down_path, middle, up_path = layout
+    found, lvl = set(), 0
+    for blk in list(down_path) + [middle] + list(up_path):
+        for kind, _ in blk:
+            if kind == "spatial":
+                found.add(lvl)
+            elif kind == "down":
+                lvl += 1
+            elif kind == "up":
+                lvl -= 1
+    return sorted(found)
+
+
 _Arena = ops.Arena
 
 
@@ -289,6 +305,7 @@ class UNetModel(nn.Module):
         # reference openaimodel3d.py:596): _cat_plan[u] = (channels of h, channels of the skip)
         self._cat_plan = self._make_cat_plan()
         self._freeu = None                      # enable_freeu's arguments; None: not one launch is added
+        self._token_ds = None                   # enable_token_downsampling's arguments; None: attn1 runs on the fused qkv
         attach_params(self, _shape_table(self._cfg))
         self._packed = None
         self._arena = _Arena()
@@ -331,6 +348,52 @@ class UNetModel(nn.Module):
             self.disable_freeu()
         else:
             self.enable_freeu(**cfg)
+        return prev
+
+    # ------------------------------------------------------------------ K/V token downsampling
+    def enable_token_downsampling(self, factor=2, levels=(0,), mode="nearest"):
+        """Token downsampling ("ToDo", Smith et al., IJCAI 2024; not in the reference) in the spatial transformers' attn1 at the
+        resolution `levels` (0 = the latent's own resolution; level l has ceil(H / 2^l) x ceil(W / 2^l) tokens per frame): the
+        queries stay at full resolution, the keys and values are projected from the norm1'd tokens pooled by `factor` per frame
+        - mode "nearest" (the paper's form) keeps tokens [::factor, ::factor], "mean" averages each factor x factor cell, clipped
+        at the border. The score matrix and the K/V projection shrink by factor^2; the softmax scale and everything downstream
+        of the attention are unchanged. Temporal attention and cross-attention are not affected.
+
+        The setting decides which kernels a forward launches: a graph-captured run (FusedRun and what builds on it) keeps the
+        setting it was captured with until it is re-created; eager calls see a change at once."""
+        if isinstance(factor, bool) or not isinstance(factor, int) or not 2 <= factor <= 8:
+            raise ValueError(f"enable_token_downsampling: factor must be an int in 2..8, got {factor!r}")
+        if mode not in tuple(ops.POOL_MODES):
+            raise ValueError(f"enable_token_downsampling: mode must be one of {tuple(ops.POOL_MODES)}, got {mode!r}")
+        if not isinstance(levels, (tuple, list, set, frozenset, range)):
+            raise ValueError(f"enable_token_downsampling: levels must be a tuple, list or set of ints, got {levels!r}")
+        lv = list(levels)
+        if not lv:
+            raise ValueError("enable_token_downsampling: levels must not be empty")
+        have = spatial_levels(self._layout)
+        for l in lv:
+            if isinstance(l, bool) or not isinstance(l, int) or not 0 <= l < len(self.channel_mult):
+                raise ValueError(f"enable_token_downsampling: level {l!r} is not an int in range({len(self.channel_mult)})")
+            if l not in have:
+                raise ValueError(f"enable_token_downsampling: level {l} holds no spatial transformer (levels with one: {have})")
+        self._token_ds = dict(factor=factor, levels=tuple(sorted(set(lv))), mode=mode)
+
+    def disable_token_downsampling(self):
+        self._token_ds = None
+
+    @property
+    def token_downsampling(self):
+        """The enable_token_downsampling arguments in force (a dict copy), or None."""
+        return None if self._token_ds is None else dict(self._token_ds)
+
+    def set_token_downsampling(self, cfg):
+        """enable_token_downsampling(**cfg) or, for None, disable_token_downsampling(); returns the previous setting (what
+        restores it)."""
+        prev = self.token_downsampling
+        if cfg is None:
+            self.disable_token_downsampling()
+        else:
+            self.enable_token_downsampling(**cfg)
         return prev
 
     # ------------------------------------------------------------------ weights -> device layout
@@ -451,7 +514,24 @@ class UNetModel(nn.Module):
     def packed(self, device):
         if self._packed is None or self._packed["device"] != device:
             self._packed = self._pack(device)
+        if self._token_ds is not None and not self._packed.get("attn1_split"):
+            self._split_attn1(self._packed)
         return self._packed
+
+    @staticmethod
+    def _split_attn1(P):
+        """Per spatial attn1 of a packed table the q [C, C] and kv [2C, C] weights beside its qkv [3C, C]: rows of the bf16
+        copy already made, so the split projections multiply by the very weights the fused one does. Built on the first
+        forward with token downsampling on; part of the table, so a weight load drops them with the rest."""
+        for blocks in P["in"] + [P["mid"]] + P["out"]:
+            for W in blocks:
+                if "blk" in W and "q2" in W["blk"]:                # a SpatialTransformer (its attn2 is a cross-attention)
+                    Wa = W["blk"]["attn1"]
+                    qkv = Wa["qkv"]
+                    Cc = qkv.N // 3
+                    Wa["q"] = PackedWeight._finish(qkv.w[:Cc], None, qkv.w.device, qkv.K, 1)
+                    Wa["kv"] = PackedWeight._finish(qkv.w[Cc:3 * Cc], None, qkv.w.device, qkv.K, 1)
+        P["attn1_split"] = True
 
     # ------------------------------------------------------------------ layer recipes on rows
     def _gn(self, x, wb, tag, *, n_inst, rpi, eps, silu):
@@ -526,6 +606,19 @@ class UNetModel(nn.Module):
     def _attn_self_spatial(self, Wa, ln, h, g, heads):
         A = self._arena
         M, dev, Cc = h.shape[0], h.device, heads * 64
+        td = self._token_ds
+        if td is not None and g["lvl"] in td["levels"]:
+            # token downsampling: q from every token, k / v from the norm1'd tokens of the pooled grid (Lk = Hp * Wp)
+            f = td["factor"]
+            Hp, Wp = ops.pooled_grid(g["H"], g["W"], f)
+            Mp = g["F"] * Hp * Wp
+            q = self._ln_linear(h, ln, Wa["q"], A.get("todo_q", M, Cc, device=dev))
+            p = ops.ln_pool_tokens(h, A.get("todo_pool", Mp, Cc, device=dev), ln[0], ln[1], F=g["F"], H=g["H"], W=g["W"],
+                                   factor=f, mode=td["mode"], eps=1e-5)
+            kv = _linear(p, Wa["kv"], A.get("todo_kv", Mp, 2 * Cc, device=dev))
+            att = A.get("att", M, Cc, device=dev)
+            ops.flash_attn(q, kv[:, :Cc], kv[:, Cc:], att, batch=g["F"], heads=heads, Lq=g["HW"], Lk=Hp * Wp, scale=0.125)
+            return self._lin_res(att, Wa["out"], h, h)
         qkv = self._ln_linear(h, ln, Wa["qkv"], A.get("qkv", M, 3 * Cc, device=dev))
         att = A.get("att", M, Cc, device=dev)
         ops.flash_attn(qkv[:, :Cc], qkv[:, Cc:2 * Cc], qkv[:, 2 * Cc:], att, batch=g["F"], heads=heads, Lq=g["HW"],
@@ -656,12 +749,14 @@ class UNetModel(nn.Module):
                 rows = g["F"] * OH * OW
                 h = ops.gemm(h, W["conv"], final(rows, a["ch"]) if last else A.get(out_tag, rows, a["ch"], device=dev), conv=conv)
                 g["H"], g["W"], g["HW"] = OH, OW, OH * OW
+                g["lvl"] += 1
             elif kind == "up":
                 OH, OW = g["H"] * 2, g["W"] * 2
                 conv = dict(IH=g["H"], IW=g["W"], OH=OH, OW=OW, stride=1, pad=1, ups=1)
                 rows = g["F"] * OH * OW
                 h = ops.gemm(h, W["conv"], final(rows, a["ch"]) if last else A.get(out_tag, rows, a["ch"], device=dev), conv=conv)
                 g["H"], g["W"], g["HW"] = OH, OW, OH * OW
+                g["lvl"] -= 1
         return h
 
     # ------------------------------------------------------------------ forward on rows
@@ -697,7 +792,7 @@ class UNetModel(nn.Module):
             ops.gemv_small(hid, Wt["fps2"], emb, accumulate=True)
         if ctx_kv is not None and ctx_kv.get("__gen__") != Wt["gen"]:
             ctx_kv = None                      # projected with weights that have been repacked since: project here
-        g = dict(B=B, T=T, F=B * T, H=H, W=W, HW=H * W, emb=emb, ctx=ctx_rows, Lc=Lc, n_text=n_text, ctx_kv=ctx_kv)
+        g = dict(B=B, T=T, F=B * T, H=H, W=W, HW=H * W, lvl=0, emb=emb, ctx=ctx_rows, Lc=Lc, n_text=n_text, ctx_kv=ctx_kv)
         down_path, middle, up_path = self._layout
         n_up = len(up_path)
 

@@ -389,6 +389,43 @@ def layernorm(x, y, gamma, beta, eps=1e-5):
     return y
 
 
+POOL_MODES = {"nearest": 0, "mean": 1}
+
+
+def pooled_grid(H, W, factor):
+    """(Hp, Wp) = (ceil(H / factor), ceil(W / factor)): the token grid ln_pool_tokens writes."""
+    return (H + factor - 1) // factor, (W + factor - 1) // factor
+
+
+def ln_pool_tokens(x, y, gamma, beta, *, F, H, W, factor, mode, eps=1e-5):
+    """y = the LayerNorm'd tokens of x on the grid pooled by `factor`: x bf16 rows [F*H*W, C] ordered (frame, y, x), y bf16 rows
+    [F*Hp*Wp, C] with (Hp, Wp) = pooled_grid(H, W, factor). mode "nearest": LayerNorm(x)[::factor, ::factor] per frame, the bits
+    of ops.layernorm at the kept rows; "mean": the mean of the LayerNorm'd tokens of each factor x factor cell, clipped at the
+    border (avg_pool2d, ceil_mode=True, count_include_pad=False). The K/V tokens of a spatial self-attention with token
+    downsampling (UNetModel.enable_token_downsampling); one launch, no atomics: bit-reproducible and graph-capturable."""
+    _rows(x, "x"); _rows(y, "y")
+    if mode not in POOL_MODES:
+        raise ValueError(f"ln_pool_tokens: mode must be 'nearest' or 'mean', got {mode!r}")
+    if isinstance(factor, bool) or not isinstance(factor, int) or not 2 <= factor <= 8:
+        raise ValueError(f"ln_pool_tokens: factor must be an int in 2..8, got {factor!r}")
+    Cc = gamma.numel()
+    if Cc % 8 or not 0 < Cc <= 2048:
+        raise ValueError(f"ln_pool_tokens: C must be a multiple of 8 and at most 2048, got {Cc}")
+    if min(F, H, W) < 1 or x.shape[0] != F * H * W:
+        raise ValueError(f"ln_pool_tokens: x is {tuple(x.shape)}, expected [F*H*W, C] = [{F * H * W}, {Cc}]")
+    Hp, Wp = pooled_grid(H, W, factor)
+    _need_rows(x, F * H * W, Cc, "x"); _need_rows(y, F * Hp * Wp, Cc, "y"); _need(beta, Cc, "beta")
+    for t, n in ((x, "x"), (y, "y")):
+        if t.stride(0) % 8 or t.data_ptr() % 16:
+            raise ValueError(f"ln_pool_tokens: {n} needs a row stride that is a multiple of 8 and a 16-byte aligned start, got "
+                             f"stride {t.stride(0)}, address % 16 = {t.data_ptr() % 16}")
+    cell = 1 if mode == "nearest" else factor * factor
+    _launch(f"ln_pool_tokens({mode})", 0.0, 2.0 * F * Hp * Wp * Cc * (min(cell, H * W) + 1), _hip.lib().dc_ln_pool_tokens, _ptr(x),
+            x.stride(0), _ptr(y), y.stride(0), _ptr(gamma), _ptr(beta), F, H, W, Cc, factor, POOL_MODES[mode], eps, stream_ptr(),
+            tag=f"F{F} {H}x{W} C{Cc} f{factor}")
+    return y
+
+
 def flash_attn(q, k, v, o, *, batch, heads, Lq, Lk, scale, accumulate=False, acc_scale=1.0, q_bstride=None,
                kv_bstride=None):
     """q/o rows [batch*Lq, >=heads*64]; k/v rows [batch*Lk, ...] (views into a fused qkv buffer are fine).

@@ -18,7 +18,7 @@ import time
 
 import torch
 
-from ...lvdm.models.samplers.ddim import DDIMSampler, freeu_scope
+from ...lvdm.models.samplers.ddim import DDIMSampler, freeu_scope, token_downsampling_scope
 from ...lvdm.models.samplers.ddim_multiplecond import DDIMSampler as DDIMSampler_multicond
 from . import inference as I
 from .inference import build_conditioning, get_latent_z
@@ -39,7 +39,8 @@ _REFUSED = ("loop", "interp", "num_frames", "window_stride")
 def video_guided_synthesis(model, prompts, videos, source, noise_shape, n_samples=1, ddim_steps=50, ddim_eta=0.0,
                            unconditional_guidance_scale=1.0, cfg_img=None, fs=None, text_input=False,
                            multiple_cond_cfg=False, timestep_spacing="uniform", guidance_rescale=0.0, strength=0.6,
-                           invert=True, source_prompts=None, freeu=None, apg=None, **kwargs):
+                           invert=True, source_prompts=None, freeu=None, apg=None, token_downsampling=None,
+                           **kwargs):
     """Returns [batch, n_samples, c, t, h, w] decoded frames. `videos` [b, 3, t, h, w] is what `load_data_prompts` gives for
     the EDITED first frame (that frame over all frames), `source` [b, 3, t, h, w] what `load_video_batch` gives for the
     clip to edit; the other arguments are `image_guided_synthesis`'s. n = strength_steps(strength, ddim_steps) steps run.
@@ -58,10 +59,13 @@ def video_guided_synthesis(model, prompts, videos, source, noise_shape, n_sample
     and the denoise alike, so that the denoise runs the model the inversion inverted; the model's previous setting is back
     when the call returns or raises.
     `apg`: None, or dict(eta=0.0, norm_threshold=None, momentum=0.0, space="x0") - adaptive projected guidance for the
-    denoise (`DDIMSampler.decode`); the inversion runs at guidance scale 1 and has none."""
+    denoise (`DDIMSampler.decode`); the inversion runs at guidance scale 1 and has none.
+    `token_downsampling`: None, or dict(factor=2, levels=(0,), mode="nearest") - K/V token downsampling in the spatial
+    self-attentions (UNetModel.enable_token_downsampling), like `freeu` for the inversion and the denoise alike, and restored
+    like it."""
     if apg is not None:
         kwargs.update(apg=apg)
-    with freeu_scope(model, freeu):
+    with freeu_scope(model, freeu), token_downsampling_scope(model, token_downsampling):
         return _video_guided_synthesis(model, prompts, videos, source, noise_shape, n_samples, ddim_steps, ddim_eta,
                                        unconditional_guidance_scale, cfg_img, fs, text_input, multiple_cond_cfg,
                                        timestep_spacing, guidance_rescale, strength, invert, source_prompts, **kwargs)
@@ -166,6 +170,7 @@ def run_edit(args, gpu_num, gpu_no, device=None):
     extra = {k: getattr(args, k) for k in ("sampler", "num_frames", "window_stride", "loop", "interp")}
     extra["freeu"] = I.freeu_from_args(args)
     extra["apg"] = I.apg_from_args(args)
+    extra["token_downsampling"] = I.token_downsampling_from_args(args)
     save_kw = dict(container=args.container, quality=args.quality)
     written = []
     start = time.time()

@@ -27,7 +27,7 @@ from .inference import get_latent_z, load_model_checkpoint, load_prompts  # noqa
 
 @torch.no_grad()
 def batch_ddim_sampling(model, cond, noise_shape, n_samples=1, ddim_steps=50, ddim_eta=1.0, cfg_scale=1.0,
-                        temporal_cfg_scale=None, freeu=None, apg=None, **kwargs):
+                        temporal_cfg_scale=None, freeu=None, apg=None, token_downsampling=None, **kwargs):
     """funcs.py:14-80. `cond` is {"c_crossattn": [...], "c_concat": [...], "fs": tensor}; "fs" is taken out of it (the caller's
     dict comes back without it, as in the reference). A latent width of 32 (the 256 model) samples with "uniform" spacing and no
     guidance rescale, any other width with "uniform_trailing" and 0.7. With cfg_scale != 1 the unconditional branch is a copy of
@@ -42,9 +42,14 @@ def batch_ddim_sampling(model, cond, noise_shape, n_samples=1, ddim_steps=50, dd
     (UNetModel.enable_freeu); the model's previous setting is back when the call returns or raises.
     `apg` (not in the reference): None, or dict(eta=0.0, norm_threshold=None, momentum=0.0, space="x0") - adaptive projected
     guidance in place of the plain CFG combine (lvdm/models/samplers/ddim.py); it needs cfg_scale != 1, and it
-    takes the place of the guidance rescale of 0.7, which is then not applied."""
+    takes the place of the guidance rescale of 0.7, which is then not applied.
+    `token_downsampling` (not in the reference): None, or dict(factor=2, levels=(0,), mode="nearest") - K/V token downsampling in
+    the spatial self-attentions of those levels for this call (UNetModel.enable_token_downsampling); restored
+    like `freeu`."""
     if freeu is not None:
         kwargs.update(freeu=freeu)
+    if token_downsampling is not None:
+        kwargs.update(token_downsampling=token_downsampling)
     if apg is not None:
         kwargs.update(apg=apg)
     name = kwargs.pop("sampler", "ddim")

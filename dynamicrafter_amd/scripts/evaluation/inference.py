@@ -121,7 +121,7 @@ def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddi
                            multiple_cond_cfg=False, loop=False, interp=False, timestep_spacing="uniform",
                            guidance_rescale=0.0, use_fixed_scheduler=False, sampler="ddim", num_frames=None,
                            window_stride=None, window_weights="triangle", window_shift=0, freeu=None, apg=None,
-                           **kwargs):
+                           token_downsampling=None, **kwargs):
     """inference.py:216-313. Returns [batch, n_samples, c, t, h, w] decoded frames.
 
     `use_fixed_scheduler` is accepted and ignored: the fork's "fixed" sampler only patches sigma so that
@@ -142,11 +142,16 @@ def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddi
     (UNetModel.enable_freeu); the model's previous setting is back when the call returns or raises.
     `apg` (not in the reference): None, or dict(eta=0.0, norm_threshold=None, momentum=0.0, space="x0") - adaptive projected
     guidance in place of the plain CFG combine (lvdm/models/samplers/ddim.py). Two guidance branches only, and
-    not with guidance_rescale > 0."""
+    not with guidance_rescale > 0.
+    `token_downsampling` (not in the reference): None, or dict(factor=2, levels=(0,), mode="nearest") - K/V token downsampling in
+    the spatial self-attentions of those resolution levels for this call (UNetModel.enable_token_downsampling, DESIGN 4.14);
+    the model's previous setting is back when the call returns or raises."""
     if freeu is not None:
         kwargs.update(freeu=freeu)
     if apg is not None:
         kwargs.update(apg=apg)
+    if token_downsampling is not None:
+        kwargs.update(token_downsampling=token_downsampling)
     T_model = getattr(model, "temporal_length", None)
     if num_frames is not None:
         if loop or interp:
@@ -419,6 +424,8 @@ def run_inference(args, gpu_num, gpu_no, device=None):
         extra["freeu"] = freeu_from_args(args)
     if apg_from_args(args) is not None:
         extra["apg"] = apg_from_args(args)
+    if token_downsampling_from_args(args) is not None:
+        extra["token_downsampling"] = token_downsampling_from_args(args)
     save_kw = dict(container=getattr(args, "container", "apng"), quality=getattr(args, "quality", 90))
     written = []
     start = time.time()
@@ -490,7 +497,28 @@ def get_parser():
                         "0 15 -0.5); NORM_THRESHOLD <= 0 switches the clipping off; needs --guidance_rescale 0; default off")
     parser.add_argument("--apg_space", type=str, default=argparse.SUPPRESS, choices=("x0", "model"), help="where APG projects: "
                         "x0 = the denoised prediction (default, the paper), model = the raw output (diffusers)")
+    # likewise the three token-downsampling flags (token_downsampling_from_args)
+    parser.add_argument("--token_downsampling", type=int, default=argparse.SUPPRESS, choices=tuple(range(2, 9)), metavar="FACTOR",
+                        help="K/V token downsampling (ToDo) in the spatial self-attentions: keys and values from the tokens "
+                        "subsampled by FACTOR (2..8) per axis; default off")
+    parser.add_argument("--token_downsampling_levels", type=int, nargs="+", default=argparse.SUPPRESS, metavar="L",
+                        help="resolution levels it acts on (0 = the latent's own resolution; default 0)")
+    parser.add_argument("--token_downsampling_mode", type=str, default=argparse.SUPPRESS, choices=("nearest", "mean"),
+                        help="nearest = every FACTOR-th token (default, the paper), mean = the average of each FACTOR x FACTOR cell")
     return parser
+
+
+def token_downsampling_from_args(args):
+    """--token_downsampling FACTOR / --token_downsampling_levels / --token_downsampling_mode as the `token_downsampling=` dict
+    of image_guided_synthesis, or None. The two secondary flags without FACTOR are an error, not a silent no-op."""
+    f = getattr(args, "token_downsampling", None)
+    if f is None:
+        given = [k for k in ("token_downsampling_levels", "token_downsampling_mode") if hasattr(args, k)]
+        if given:
+            raise ValueError(f"--{given[0]} needs --token_downsampling FACTOR")
+        return None
+    return dict(factor=f, levels=tuple(getattr(args, "token_downsampling_levels", (0,))),
+                mode=getattr(args, "token_downsampling_mode", "nearest"))
 
 
 def apg_from_args(args):

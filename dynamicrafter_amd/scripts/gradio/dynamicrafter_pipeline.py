@@ -74,6 +74,14 @@ class DynamiCrafterImg2VideoPipeline:
     def disable_freeu(self):
         self.model.model.diffusion_model.disable_freeu()
 
+    def enable_token_downsampling(self, factor=2, levels=(0,), mode="nearest"):
+        """K/V token downsampling in the UNet's spatial self-attentions for every later call of the pipeline
+        (UNetModel.enable_token_downsampling). Not in the reference class."""
+        self.model.model.diffusion_model.enable_token_downsampling(factor=factor, levels=levels, mode=mode)
+
+    def disable_token_downsampling(self):
+        self.model.model.diffusion_model.disable_token_downsampling()
+
     def to(self, device, dtype=None):
         """Moves the model. `dtype` other than float32 is refused: the kernels fix their own storage types."""
         if dtype is not None and dtype != torch.float32:
@@ -175,13 +183,17 @@ class DynamiCrafterImg2VideoPipeline:
     def __call__(self, image, prompt="", negative_prompt=None, num_inference_steps=50, guidance_scale=7.5, eta=0.0,
                  frame_stride=3, num_frames=None, height=None, width=None, num_videos_per_prompt=1, generator=None,
                  latents=None, output_type="tensor", return_dict=True, callback=None, callback_steps=1,
-                 cross_attention_kwargs=None, apg=None, **kwargs):
+                 cross_attention_kwargs=None, apg=None, token_downsampling=None, **kwargs):
         """:398-530. Returns {"videos": v} (or v with return_dict=False); v is [b, 3, num_frames, height, width] as a device
         tensor ("tensor"), an ndarray ("numpy") or b lists of PIL frames ("pil"). Extra **kwargs reach DDIMSampler.sample.
         `apg` (not in the reference): dict(eta=0.0, norm_threshold=None, momentum=0.0, space="x0") for adaptive projected
-        guidance in place of plain CFG (DDIMSampler.sample's `apg=`); needs guidance_scale != 1."""
+        guidance in place of plain CFG (DDIMSampler.sample's `apg=`); needs guidance_scale != 1.
+        `token_downsampling` (not in the reference): dict(factor=2, levels=(0,), mode="nearest") for K/V token downsampling in
+        the spatial self-attentions during this call only (DDIMSampler.sample's `token_downsampling=`)."""
         if apg is not None:
             kwargs["apg"] = apg
+        if token_downsampling is not None:
+            kwargs["token_downsampling"] = token_downsampling
         if isinstance(prompt, str):
             prompt = [prompt]
         batch_size = len(prompt)

@@ -111,6 +111,22 @@ int64_t dc_groupnorm_workspace_bytes(int n_inst, int groups, int rows_per_inst);
 int dc_layernorm(const uint16_t* x, int ldx, uint16_t* y, int ldy, const float* gamma, const float* beta,
                  int rows, int C, float eps, void* stream);
 
+/* LayerNorm + spatial token pooling: the K/V tokens of a spatial self-attention with token downsampling ("ToDo", Smith et
+ * al., IJCAI 2024; not in the reference). x: bf16 rows [F*H*W][ldx], rows ordered (frame, y, x'); y: bf16 rows [F*Hp*Wp][ldy]
+ * with Hp = ceil(H / factor), Wp = ceil(W / factor), ordered (frame, yp, xp); gamma / beta fp32 [C].
+ *   mode 0 (nearest): y[yp][xp] = LN(x[yp factor][xp factor]), the strided slice n[::f, ::f]; only the kept rows are read and the
+ *                     output equals the corresponding rows of dc_layernorm bit for bit.
+ *   mode 1 (mean):    y[yp][xp] = mean of LN(x[.][.]) over the cell [yp factor, min(H, yp factor + factor)) x [xp factor, min(W,
+ *                     xp factor + factor)): each token normalised in fp32, summed in (y, x') order, times 1 / (tokens in the
+ *                     cell), one rounding to bf16 (avg_pool2d with ceil_mode=True, count_include_pad=False).
+ * One wave per output token, 16-byte loads and stores, no atomics, no scratch: capturable, bit-reproducible.
+ * DC_ERR_ARG: a null pointer. DC_ERR_SHAPE: C % 8 != 0 or C > 2048 (dc_layernorm's limits), a row stride that is no multiple
+ * of 8 or below C, x or y not 16-byte aligned, F, H or W < 1, F*H*W >= 2^31, factor outside 2..8, mode outside {0, 1}.
+ * replaces, for to_k / to_v of attn1 only, nn.LayerNorm norm1 lvdm/modules/attention.py:225-227,243 followed by the slice or
+ * F.avg_pool2d of the token grid that the published ToDo patch applies ahead of CrossAttention.to_k / to_v (:75-76) */
+int dc_ln_pool_tokens(const uint16_t* x, int ldx, uint16_t* y, int ldy, const float* gamma, const float* beta, int F, int H,
+                      int W, int C, int factor, int mode, float eps, void* stream);
+
 /* softmax(q k^T * scale) v, head_dim 64, flash-style (no score matrix in HBM).
  * q rows: [batch][Lq] at q + (b*q_bstride + i)*ldq + h*64 ; k/v rows: [batch][Lk] likewise with kv_bstride.
  * accumulate != 0: o += acc_scale * result (image cross-attention branch), else o = result.
