@@ -20,27 +20,21 @@ behaves as the reference's, including the 3-branch guidance of ddim_multiplecond
   * `encode` (not in the reference, which leaves it as a TODO at :179) is DDIM inversion: InvertRun below, one
     dc_ddim_invert_step per step. `decode` and `ddim_sampling(timesteps=k)` run the last n steps of the schedule on the
     same fused path as `sample` (a FusedRun over the tail of the execution-order tables), DESIGN 4.11.
-  * `freeu=dict(s1=, s2=, b1=, b2=, version=)` (not in the reference) on `sample`, `ddim_sampling`, `decode` and `encode`
-    runs that call with FreeU on the UNet (UNetModel.enable_freeu) and puts the model's previous setting
-    back afterwards, also when the call raises; None (default) leaves the model's setting as it is.
-  * `apg=dict(eta=0.0, norm_threshold=None, momentum=0.0, space="x0")` (not in the reference) on `sample`, `ddim_sampling`
-    and `decode` replaces the CFG combine by adaptive projected guidance (Sadat et al., ICLR 2025): two launches
-    (ops.apg_guide) between the UNet and the unchanged update, which then takes the guided output as its only branch; the
-    running update lives in the run and is zeroed by rewind(). Two branches only, not with guidance_rescale (check_apg,
-    DESIGN 4.13). None (default): nothing is added.
-  * `token_downsampling=dict(factor=2, levels=(0,), mode="nearest")` (not in the reference) on `sample`, `ddim_sampling`,
-    `decode` and `encode` runs that call with K/V token downsampling in the spatial self-attentions of the selected levels
-    (UNetModel.enable_token_downsampling) and puts the model's previous setting back afterwards, also when
-    the call raises; None (default) leaves the model's setting as it is.
+  * the optional dict keywords of samplers/options.py (not in the reference; None, the default, adds nothing): the model
+    settings `freeu=` and `token_downsampling=` on `sample`, `ddim_sampling`, `decode` and `encode` are in force on the UNet
+    for that call and the model's previous setting is back afterwards, also when the call raises; the run
+    setting `apg=` on `sample`, `ddim_sampling` and `decode` replaces the CFG combine by adaptive projected guidance (Sadat
+    et al., ICLR 2025): two launches (ops.apg_guide) between the UNet and the unchanged update, which then takes the guided
+    output as its only branch; the running update lives in the run and is zeroed by rewind(). Two branches only, not with
+    guidance_rescale (check_apg).
 """
-import contextlib
-import functools
-
 import numpy as np
 import torch
 
 from .... import _hip, ops
 from ..utils_diffusion import make_ddim_sampling_parameters, make_ddim_timesteps
+from . import options
+from .options import OPTIONS, takes_model_settings
 from .windows import pad_plan, window_plan, windows_per_call
 
 
@@ -73,81 +67,14 @@ def _step_inputs(img, S, noises, mask, x0, q_noises, clean_cond, long_branches=N
     return noises, blend
 
 
-@contextlib.contextmanager
-def freeu_scope(model, freeu):
-    """Run a block with `freeu` (enable_freeu's arguments as a dict) on the UNet of `model` (a LatentDiffusion: its
-    model.diffusion_model, or a UNetModel itself) and restore the setting that was in force before, whatever happens
-    inside. None changes nothing. A run captured inside the block keeps FreeU in its graph after the block ends."""
-    if freeu is None:
-        yield
-        return
-    net = getattr(getattr(model, "model", None), "diffusion_model", model)
-    if not hasattr(net, "set_freeu"):
-        raise ValueError(f"freeu=: {type(net).__name__} has no FreeU (expected the HIP UNetModel)")
-    prev = net.set_freeu(dict(freeu))          # validates before anything runs
-    try:
-        yield
-    finally:
-        net.set_freeu(prev)
-
-
-def _takes_freeu(fn):
-    """Gives a sampler method the keyword `freeu=` (freeu_scope around the whole call)."""
-    @functools.wraps(fn)
-    def wrapped(self, *args, freeu=None, **kwargs):
-        with freeu_scope(self.model, freeu):
-            return fn(self, *args, **kwargs)
-    return wrapped
-
-
-TOKEN_DS_KEYS = ("factor", "levels", "mode")
-
-
-@contextlib.contextmanager
-def token_downsampling_scope(model, cfg):
-    """Run a block with K/V token downsampling `cfg` (enable_token_downsampling's arguments as a dict: factor, levels, mode)
-    on the UNet of `model` (a LatentDiffusion: its model.diffusion_model, or a UNetModel itself) and restore the setting that
-    was in force before, whatever happens inside. None changes nothing. A run captured inside the block keeps the setting in
-    its graph after the block ends."""
-    if cfg is None:
-        yield
-        return
-    if not isinstance(cfg, dict):
-        raise ValueError(f"token_downsampling= takes a dict with keys {list(TOKEN_DS_KEYS)} or None, got {type(cfg).__name__}")
-    unknown = sorted(set(cfg) - set(TOKEN_DS_KEYS))
-    if unknown:
-        raise ValueError(f"token_downsampling=: unknown keys {unknown}; known: {list(TOKEN_DS_KEYS)}")
-    net = getattr(getattr(model, "model", None), "diffusion_model", model)
-    if not hasattr(net, "set_token_downsampling"):
-        raise ValueError(f"token_downsampling=: {type(net).__name__} has no token downsampling (expected the HIP UNetModel)")
-    prev = net.set_token_downsampling(dict(cfg))          # validates before anything runs
-    try:
-        yield
-    finally:
-        net.set_token_downsampling(prev)
-
-
-def _takes_token_downsampling(fn):
-    """Gives a sampler method the keyword `token_downsampling=` (token_downsampling_scope around the whole call)."""
-    @functools.wraps(fn)
-    def wrapped(self, *args, token_downsampling=None, **kwargs):
-        with token_downsampling_scope(self.model, token_downsampling):
-            return fn(self, *args, **kwargs)
-    return wrapped
-
-
-APG_DEFAULTS = dict(eta=0.0, norm_threshold=None, momentum=0.0, space="x0")
+APG_DEFAULTS = OPTIONS["apg"].keys
 
 
 def apg_config(apg):
     """The validated, completed copy of an `apg=` dict (keys of APG_DEFAULTS), or None for None."""
     if apg is None:
         return None
-    if not isinstance(apg, dict):
-        raise ValueError(f"apg= takes a dict with keys {sorted(APG_DEFAULTS)} or None, got {type(apg).__name__}")
-    unknown = sorted(set(apg) - set(APG_DEFAULTS))
-    if unknown:
-        raise ValueError(f"apg=: unknown keys {unknown}; known: {sorted(APG_DEFAULTS)}")
+    options.check_keys(OPTIONS["apg"], apg)
     cfg = dict(APG_DEFAULTS, **apg)
     for k in ("eta", "momentum", "norm_threshold"):
         v = cfg[k]
@@ -257,6 +184,11 @@ class StepRun:
             self._enqueue()
         self.steps_done += 1
 
+    def _split(self, e):
+        """The branch-major rows `e` [nb * M, C] of a model evaluation as (e_c, e_u, e_i); None for a branch the run lacks."""
+        M = self.kw["B"] * self.kw["THW"]
+        return e[:M], e[M:2 * M] if self.nb > 1 else None, e[2 * M:3 * M] if self.nb > 2 else None
+
     def rewind(self, x_T=None):
         """Start over: the counter and the subclass's state to their initial values; optionally a new initial latent."""
         self.sync()
@@ -320,14 +252,11 @@ class FusedRun(StepRun):
             b = self.blend
             ops.mask_blend(self.img, b["x0"], b["mask"], b["q"], self.tables, step_index=self.counter,
                            clean=b["clean"], noise_step_stride=self.img.numel())
-        e = self._evaluate()
-        M = self.kw["B"] * self.kw["THW"]
-        e_u = e[M:2 * M] if self.nb > 1 else None
-        e_i = e[2 * M:3 * M] if self.nb > 2 else None
+        e_c, e_u, e_i = self._split(self._evaluate())
         if self.apg is None:
-            self._update(e[:M], e_u, e_i)
+            self._update(e_c, e_u, e_i)
         else:
-            self._update(ops.apg_guide(self.tables, e[:M], e_u, self.img, self.apg_m, self.apg_out, self.apg_ws,
+            self._update(ops.apg_guide(self.tables, e_c, e_u, self.img, self.apg_m, self.apg_out, self.apg_ws,
                                        step_index=self.counter, **self.apg_kw), None, None)
         ops.advance_counter(self.counter)
 
@@ -368,10 +297,7 @@ class InvertRun(StepRun):
 
     def _enqueue(self):
         e = self.model.apply_model_rows(self.img, self.prep, self.t_table, t_index=self.counter)
-        M = self.kw["B"] * self.kw["THW"]
-        e_u = e[M:2 * M] if self.nb > 1 else None
-        e_i = e[2 * M:3 * M] if self.nb > 2 else None
-        ops.ddim_invert_step(self.tables, e[:M], e_u, e_i, self.img, self.img, self.pred_x0, self.ws,
+        ops.ddim_invert_step(self.tables, *self._split(e), self.img, self.img, self.pred_x0, self.ws,
                              step_index=self.counter, **self.kw)
         ops.advance_counter(self.counter)
 
@@ -540,6 +466,10 @@ class DDIMSampler(object):
                 br.append(uc2)
         return br
 
+    def _fused(self, branches):
+        """Fused path (a StepRun on the model's batched entry) or generic path (separate apply_model calls)?"""
+        return hasattr(self.model, "apply_model_rows") and all(isinstance(c, dict) for c in branches)
+
     # ------------------------------------------------------------------ what a subclass's update changes (dpm_solver.py)
     _run_class = FusedRun
 
@@ -587,8 +517,7 @@ class DDIMSampler(object):
         subset_end = int(min(timesteps / S, 1) * S) - 1
         return len(range(S)[:subset_end])
 
-    @_takes_token_downsampling
-    @_takes_freeu
+    @takes_model_settings
     def _denoise(self, n, cond, shape, x_T=None, callback=None, mask=None, x0=None, img_callback=None, log_every_t=100,
                  temperature=1., unconditional_guidance_scale=1., unconditional_conditioning=None, fs=None,
                  guidance_rescale=0.0, noises=None, use_graph=False, window_stride=None, window_weights="triangle",
@@ -646,7 +575,7 @@ class DDIMSampler(object):
             g.update(apg=apg, apg_state={})
         intermediates = {"x_inter": [img.clone()], "pred_x0": [img.clone()]}
         run = None
-        if hasattr(m, "apply_model_rows") and all(isinstance(c, dict) for c in branches):
+        if self._fused(branches):
             cls, wkw = (self._run_class, {}) if window is None else (windowed(self._run_class), dict(window=window))
             run = cls(self, img, branches, fs=fs, noises=noises, cfg_scale=unconditional_guidance_scale,
                       cfg_img=kwargs.get("cfg_img"), guidance_rescale=guidance_rescale, temperature=temperature,
@@ -746,16 +675,19 @@ class DDIMSampler(object):
     def decode(self, x_latent, cond, t_start, unconditional_guidance_scale=1.0, unconditional_conditioning=None,
                use_original_steps=False, callback=None, *, fs=None, guidance_rescale=0.0, cfg_img=None,
                unconditional_conditioning_img_nonetext=None, noises=None, temperature=1., mask=None, x0=None,
-               q_noises=None, use_graph=False, img_callback=None, log_every_t=100, freeu=None, apg=None,
-               token_downsampling=None):
+               q_noises=None, use_graph=False, img_callback=None, log_every_t=100, **sampling_options):
         """ddim.py:281-301: run the last t_start DDIM steps from x_latent (at level ddim_alphas[t_start - 1]) and return
         the result. The steps are those of `sample`, on the same path (a partial FusedRun when the model has the batched
         entry), so the keyword-only options mean what they mean there; `noises` / `q_noises` are [t_start, ...], indexed
-        by the executed step. Without `fs` none is passed to the model, as in the reference."""
+        by the executed step. Without `fs` none is passed to the model, as in the reference. `sampling_options`: the
+        keywords of samplers/options.py (`freeu=`, `apg=`, `token_downsampling=`) and no other."""
         if use_original_steps:
             raise NotImplementedError
+        unexpected = sorted(set(sampling_options) - set(OPTIONS))
+        if unexpected:
+            raise TypeError(f"decode() got an unexpected keyword argument {unexpected[0]!r}")
         n = len(self.ddim_timesteps[:t_start])
-        kw = {}
+        kw = sampling_options
         if cfg_img is not None:
             kw["cfg_img"] = cfg_img
         if unconditional_conditioning_img_nonetext is not None:
@@ -766,13 +698,11 @@ class DDIMSampler(object):
                                  img_callback=img_callback, log_every_t=log_every_t, temperature=temperature,
                                  unconditional_guidance_scale=unconditional_guidance_scale,
                                  unconditional_conditioning=unconditional_conditioning, fs=fs,
-                                 guidance_rescale=guidance_rescale, noises=noises, use_graph=use_graph, freeu=freeu, apg=apg,
-                                 token_downsampling=token_downsampling, **kw)
+                                 guidance_rescale=guidance_rescale, noises=noises, use_graph=use_graph, **kw)
         return x_dec
 
     @torch.no_grad()
-    @_takes_token_downsampling
-    @_takes_freeu
+    @takes_model_settings
     def encode(self, x0, c, t_enc, use_original_steps=False, return_intermediates=None,
                unconditional_guidance_scale=1.0, unconditional_conditioning=None, callback=None, *, fs=None,
                guidance_rescale=0.0, use_graph=False, **kwargs):
@@ -785,8 +715,10 @@ class DDIMSampler(object):
         with return_intermediates = r the latent and pred_x0 after every max(t_enc // r, 1)-th step and after the last."""
         if use_original_steps:
             raise NotImplementedError("encode runs on the DDIM timesteps only")
-        if "apg" in kwargs:
-            raise ValueError("encode: apg= is a sampling-time guidance with a running state; an inversion under it is not defined")
+        for opt in options.of_kind(options.RUN_SETTING):    # a run setting with a running state has no inversion
+            if opt.name in kwargs:
+                raise ValueError(f"encode: {opt.name}= is a sampling-time guidance with a running state; an inversion under it "
+                                 f"is not defined")
         if kwargs.get("window_stride") is not None:
             raise ValueError("encode: windowed (long-clip) inversion is not defined")
         S = self.ddim_timesteps.shape[0]
@@ -803,7 +735,7 @@ class DDIMSampler(object):
         inter = {"x_inter": [], "pred_x0": []}
         every = max(n // int(return_intermediates), 1) if return_intermediates else 0
         run = None
-        if hasattr(m, "apply_model_rows") and all(isinstance(b, dict) for b in branches):
+        if self._fused(branches):
             run = InvertRun(self, img, branches, n, fs=fs, cfg_scale=unconditional_guidance_scale, cfg_img=cfg_img,
                             guidance_rescale=guidance_rescale)
             if use_graph:

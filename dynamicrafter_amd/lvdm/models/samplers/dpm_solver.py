@@ -28,6 +28,7 @@ import torch
 
 from .... import ops
 from .ddim import DDIMSampler, FusedRun, _update_kw, apg_generic
+from .ddim_multiplecond import DDIMSampler as DDIMSampler_multicond
 
 SOLVERS = ("dpmpp_2m", "dpmpp_2m_sde")
 LOWER_ORDER_FINAL_BELOW = 15
@@ -149,3 +150,13 @@ class DPMSolverSampler(DDIMSampler):
         if kwargs.get("timesteps") is not None or (len(args) > 3 and args[3] is not None):
             raise NotImplementedError("timesteps= (a partial run) is implemented for DDIMSampler only")
         return super().ddim_sampling(cond, shape, *args, **kwargs)
+
+
+def make_sampler(model, name="ddim", multiple_cond_cfg=False):
+    """The sampler a harness function's `sampler=` names: "ddim" (the reference's; its ddim_multiplecond class with
+    `multiple_cond_cfg`) or one of SOLVERS."""
+    if name == "ddim":
+        return DDIMSampler_multicond(model) if multiple_cond_cfg else DDIMSampler(model)
+    if name in SOLVERS:
+        return DPMSolverSampler(model, solver=name)
+    raise ValueError(f"sampler must be 'ddim' or one of {SOLVERS}, got {name!r}")

@@ -341,14 +341,17 @@ class UNetModel(nn.Module):
         """The enable_freeu arguments in force (a dict copy), or None."""
         return None if self._freeu is None else dict(self._freeu)
 
-    def set_freeu(self, cfg):
-        """enable_freeu(**cfg) or, for None, disable_freeu(); returns the previous setting (what restores it)."""
-        prev = self.freeu
+    def _set_setting(self, name, cfg):
+        """set_<name>: enable_<name>(**cfg) or, for None, disable_<name>(); returns the previous setting (what restores it)."""
+        prev = getattr(self, name)
         if cfg is None:
-            self.disable_freeu()
+            getattr(self, "disable_" + name)()
         else:
-            self.enable_freeu(**cfg)
+            getattr(self, "enable_" + name)(**cfg)
         return prev
+
+    def set_freeu(self, cfg):
+        return self._set_setting("freeu", cfg)
 
     # ------------------------------------------------------------------ K/V token downsampling
     def enable_token_downsampling(self, factor=2, levels=(0,), mode="nearest"):
@@ -387,14 +390,7 @@ class UNetModel(nn.Module):
         return None if self._token_ds is None else dict(self._token_ds)
 
     def set_token_downsampling(self, cfg):
-        """enable_token_downsampling(**cfg) or, for None, disable_token_downsampling(); returns the previous setting (what
-        restores it)."""
-        prev = self.token_downsampling
-        if cfg is None:
-            self.disable_token_downsampling()
-        else:
-            self.enable_token_downsampling(**cfg)
-        return prev
+        return self._set_setting("token_downsampling", cfg)
 
     # ------------------------------------------------------------------ weights -> device layout
     def _p(self, name):

@@ -18,8 +18,8 @@ import time
 
 import torch
 
-from ...lvdm.models.samplers.ddim import DDIMSampler, freeu_scope, token_downsampling_scope
-from ...lvdm.models.samplers.ddim_multiplecond import DDIMSampler as DDIMSampler_multicond
+from ...lvdm.models.samplers import options
+from ...lvdm.models.samplers.dpm_solver import make_sampler
 from . import inference as I
 from .inference import build_conditioning, get_latent_z
 
@@ -36,6 +36,7 @@ _REFUSED = ("loop", "interp", "num_frames", "window_stride")
 
 
 @torch.no_grad()
+@options.documented
 def video_guided_synthesis(model, prompts, videos, source, noise_shape, n_samples=1, ddim_steps=50, ddim_eta=0.0,
                            unconditional_guidance_scale=1.0, cfg_img=None, fs=None, text_input=False,
                            multiple_cond_cfg=False, timestep_spacing="uniform", guidance_rescale=0.0, strength=0.6,
@@ -55,17 +56,11 @@ def video_guided_synthesis(model, prompts, videos, source, noise_shape, n_sample
     `use_graph=` goes to encode and decode; every other keyword argument goes to `DDIMSampler.decode` (`noises`,
     `temperature`, `mask`, ...). `loop`, `interp`, `num_frames`, `window_stride` and a `sampler` other than "ddim" raise
     ValueError: their conditioning or solver has no defined inverse here.
-    `freeu`: None, or dict(s1=, s2=, b1=, b2=, version=) - FreeU on the UNet (UNetModel.enable_freeu) for the inversion
-    and the denoise alike, so that the denoise runs the model the inversion inverted; the model's previous setting is back
-    when the call returns or raises.
-    `apg`: None, or dict(eta=0.0, norm_threshold=None, momentum=0.0, space="x0") - adaptive projected guidance for the
-    denoise (`DDIMSampler.decode`); the inversion runs at guidance scale 1 and has none.
-    `token_downsampling`: None, or dict(factor=2, levels=(0,), mode="nearest") - K/V token downsampling in the spatial
-    self-attentions (UNetModel.enable_token_downsampling), like `freeu` for the inversion and the denoise alike, and restored
-    like it."""
-    if apg is not None:
-        kwargs.update(apg=apg)
-    with freeu_scope(model, freeu), token_downsampling_scope(model, token_downsampling):
+    The model settings among the options below are in force for the inversion and the denoise alike, so that the denoise
+    runs the model the inversion inverted; `apg` goes to the denoise (`DDIMSampler.decode`): the inversion runs at guidance
+    scale 1 and has none."""
+    options.fold(kwargs, freeu=freeu, apg=apg, token_downsampling=token_downsampling)
+    with options.model_settings_scope(model, kwargs):
         return _video_guided_synthesis(model, prompts, videos, source, noise_shape, n_samples, ddim_steps, ddim_eta,
                                        unconditional_guidance_scale, cfg_img, fs, text_input, multiple_cond_cfg,
                                        timestep_spacing, guidance_rescale, strength, invert, source_prompts, **kwargs)
@@ -87,7 +82,7 @@ def _video_guided_synthesis(model, prompts, videos, source, noise_shape, n_sampl
     if tuple(source.shape[:1]) + tuple(source.shape[2:3]) != (noise_shape[0], noise_shape[2]):
         raise ValueError(f"video_guided_synthesis: source {tuple(source.shape)} does not hold {noise_shape[0]} clips of "
                          f"{noise_shape[2]} frames")
-    sampler = DDIMSampler_multicond(model) if multiple_cond_cfg else DDIMSampler(model)
+    sampler = make_sampler(model, "ddim", multiple_cond_cfg)
     sampler.make_schedule(ddim_num_steps=ddim_steps, ddim_discretize=timestep_spacing, ddim_eta=ddim_eta, verbose=False)
 
     batch_size = noise_shape[0]
@@ -168,9 +163,7 @@ def run_edit(args, gpu_num, gpu_no, device=None):
     print("Edits [rank:%d] %d/%d samples loaded." % (gpu_no, len(indices), len(prompt_list)))
 
     extra = {k: getattr(args, k) for k in ("sampler", "num_frames", "window_stride", "loop", "interp")}
-    extra["freeu"] = I.freeu_from_args(args)
-    extra["apg"] = I.apg_from_args(args)
-    extra["token_downsampling"] = I.token_downsampling_from_args(args)
+    extra.update(options.options_from_args(args))
     save_kw = dict(container=args.container, quality=args.quality)
     written = []
     start = time.time()

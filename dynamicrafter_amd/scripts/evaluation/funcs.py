@@ -18,14 +18,14 @@ import os
 import numpy as np
 import torch
 
-from ...lvdm.models.samplers.ddim import DDIMSampler
-from ...lvdm.models.samplers.dpm_solver import SOLVERS as DPM_SOLVERS
-from ...lvdm.models.samplers.dpm_solver import DPMSolverSampler
+from ...lvdm.models.samplers import options
+from ...lvdm.models.samplers.dpm_solver import make_sampler
 from .edit import video_guided_synthesis  # noqa: F401  (re-exported)
 from .inference import get_latent_z, load_model_checkpoint, load_prompts  # noqa: F401  (re-exported)
 
 
 @torch.no_grad()
+@options.documented
 def batch_ddim_sampling(model, cond, noise_shape, n_samples=1, ddim_steps=50, ddim_eta=1.0, cfg_scale=1.0,
                         temporal_cfg_scale=None, freeu=None, apg=None, token_downsampling=None, **kwargs):
     """funcs.py:14-80. `cond` is {"c_crossattn": [...], "c_concat": [...], "fs": tensor}; "fs" is taken out of it (the caller's
@@ -38,27 +38,9 @@ def batch_ddim_sampling(model, cond, noise_shape, n_samples=1, ddim_steps=50, dd
     its UNet swallows them unused; they are not forwarded here and `temporal_cfg_scale` has no effect. Every other keyword
     argument reaches `DDIMSampler.sample` (`x_T`, `noises`, `use_graph`, `window_stride`, ...), except `sampler=`, which picks
     the sampler class as in `image_guided_synthesis` ("ddim", "dpmpp_2m", "dpmpp_2m_sde").
-    `freeu` (not in the reference): None, or dict(s1=, s2=, b1=, b2=, version=) - FreeU on the UNet's decoder for this call
-    (UNetModel.enable_freeu); the model's previous setting is back when the call returns or raises.
-    `apg` (not in the reference): None, or dict(eta=0.0, norm_threshold=None, momentum=0.0, space="x0") - adaptive projected
-    guidance in place of the plain CFG combine (lvdm/models/samplers/ddim.py); it needs cfg_scale != 1, and it
-    takes the place of the guidance rescale of 0.7, which is then not applied.
-    `token_downsampling` (not in the reference): None, or dict(factor=2, levels=(0,), mode="nearest") - K/V token downsampling in
-    the spatial self-attentions of those levels for this call (UNetModel.enable_token_downsampling); restored
-    like `freeu`."""
-    if freeu is not None:
-        kwargs.update(freeu=freeu)
-    if token_downsampling is not None:
-        kwargs.update(token_downsampling=token_downsampling)
-    if apg is not None:
-        kwargs.update(apg=apg)
-    name = kwargs.pop("sampler", "ddim")
-    if name == "ddim":
-        ddim_sampler = DDIMSampler(model)
-    elif name in DPM_SOLVERS:
-        ddim_sampler = DPMSolverSampler(model, solver=name)
-    else:
-        raise ValueError(f"sampler must be 'ddim' or one of {DPM_SOLVERS}, got {name!r}")
+    Here `apg` takes the place of the guidance rescale of 0.7, which is then not applied."""
+    options.fold(kwargs, freeu=freeu, apg=apg, token_downsampling=token_downsampling)
+    ddim_sampler = make_sampler(model, kwargs.pop("sampler", "ddim"))
     kwargs.pop("temporal_length", None)
     kwargs.pop("conditional_guidance_scale_temporal", None)
     batch_size = noise_shape[0]

@@ -21,6 +21,7 @@ outside this package: see lvdm/modules/encoders/condition.py).
 """
 import argparse
 import datetime
+import functools
 import glob
 import os
 import random
@@ -31,10 +32,9 @@ from collections import OrderedDict, namedtuple
 import numpy as np
 import torch
 
-from ...lvdm.models.samplers.ddim import DDIMSampler
-from ...lvdm.models.samplers.ddim_multiplecond import DDIMSampler as DDIMSampler_multicond
+from ...lvdm.models.samplers import options
 from ...lvdm.models.samplers.dpm_solver import SOLVERS as DPM_SOLVERS
-from ...lvdm.models.samplers.dpm_solver import DPMSolverSampler
+from ...lvdm.models.samplers.dpm_solver import make_sampler
 
 
 def load_model_checkpoint(model, ckpt):
@@ -116,6 +116,7 @@ def build_conditioning(model, prompts, videos, unconditional_guidance_scale=1.0,
 
 
 @torch.no_grad()
+@options.documented
 def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddim_steps=50, ddim_eta=1.,
                            unconditional_guidance_scale=1.0, cfg_img=None, fs=None, text_input=False,
                            multiple_cond_cfg=False, loop=False, interp=False, timestep_spacing="uniform",
@@ -137,21 +138,8 @@ def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddi
     temporal_length // 2): the image latent is repeated over `num_frames` for c_concat, `x_T` / `noises` passed through
     are `num_frames` long, and all frames are decoded. `window_stride` alone asks for windows at the clip's own length.
     Not with `loop` / `interp`: their c_concat is zero on interior frames, so interior windows would see a conditioning
-    the model never met.
-    `freeu` (not in the reference): None, or dict(s1=, s2=, b1=, b2=, version=) - FreeU on the UNet's decoder for this call
-    (UNetModel.enable_freeu); the model's previous setting is back when the call returns or raises.
-    `apg` (not in the reference): None, or dict(eta=0.0, norm_threshold=None, momentum=0.0, space="x0") - adaptive projected
-    guidance in place of the plain CFG combine (lvdm/models/samplers/ddim.py). Two guidance branches only, and
-    not with guidance_rescale > 0.
-    `token_downsampling` (not in the reference): None, or dict(factor=2, levels=(0,), mode="nearest") - K/V token downsampling in
-    the spatial self-attentions of those resolution levels for this call (UNetModel.enable_token_downsampling, DESIGN 4.14);
-    the model's previous setting is back when the call returns or raises."""
-    if freeu is not None:
-        kwargs.update(freeu=freeu)
-    if apg is not None:
-        kwargs.update(apg=apg)
-    if token_downsampling is not None:
-        kwargs.update(token_downsampling=token_downsampling)
+    the model never met."""
+    options.fold(kwargs, freeu=freeu, apg=apg, token_downsampling=token_downsampling)
     T_model = getattr(model, "temporal_length", None)
     if num_frames is not None:
         if loop or interp:
@@ -164,12 +152,7 @@ def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddi
         noise_shape = list(noise_shape[:2]) + [num_frames] + list(noise_shape[3:])
     if window_stride is not None:
         kwargs.update(window_stride=window_stride, window_weights=window_weights, window_shift=window_shift)
-    if sampler == "ddim":
-        ddim_sampler = DDIMSampler_multicond(model) if multiple_cond_cfg else DDIMSampler(model)
-    elif sampler in DPM_SOLVERS:
-        ddim_sampler = DPMSolverSampler(model, solver=sampler)
-    else:
-        raise ValueError(f"sampler must be 'ddim' or one of {DPM_SOLVERS}, got {sampler!r}")
+    ddim_sampler = make_sampler(model, sampler, multiple_cond_cfg)
     ddim_sampler.make_schedule(ddim_num_steps=ddim_steps, ddim_discretize=timestep_spacing, ddim_eta=ddim_eta, verbose=False)
 
     batch_size = noise_shape[0]
@@ -420,12 +403,7 @@ def run_inference(args, gpu_num, gpu_no, device=None):
     filename_list_rank = [filename_list[i] for i in indices]
 
     extra = {k: getattr(args, k) for k in ("sampler", "num_frames", "window_stride") if getattr(args, k, None) is not None}
-    if freeu_from_args(args) is not None:
-        extra["freeu"] = freeu_from_args(args)
-    if apg_from_args(args) is not None:
-        extra["apg"] = apg_from_args(args)
-    if token_downsampling_from_args(args) is not None:
-        extra["token_downsampling"] = token_downsampling_from_args(args)
+    extra.update(options.options_from_args(args))
     save_kw = dict(container=getattr(args, "container", "apng"), quality=getattr(args, "quality", 90))
     written = []
     start = time.time()
@@ -484,57 +462,14 @@ def get_parser():
     parser.add_argument("--num_frames", type=int, default=None, help="clip length in latent frames; above the model's "
                         "temporal_length the sampler denoises overlapping windows")
     parser.add_argument("--window_stride", type=int, default=None, help="stride of those windows (default temporal_length // 2)")
-    # the two FreeU flags appear in the namespace only when given (freeu_from_args reads them): without them a run's arguments
-    # are what they were
-    parser.add_argument("--freeu", type=float, nargs=4, default=argparse.SUPPRESS, metavar=("S1", "S2", "B1", "B2"),
-                        help="FreeU on the UNet's decoder, diffusers' argument order (its SD-2.1 suggestion: 0.9 0.2 1.4 1.6); "
-                        "default off")
-    parser.add_argument("--freeu_version", type=int, default=argparse.SUPPRESS, choices=(1, 2), help="FreeU backbone scaling: "
-                        "1 = constant b (default), 2 = b weighted by the normalised channel mean")
-    # likewise --apg / --apg_space (apg_from_args)
-    parser.add_argument("--apg", type=float, nargs=3, default=argparse.SUPPRESS, metavar=("ETA", "NORM_THRESHOLD", "MOMENTUM"),
-                        help="adaptive projected guidance in place of plain CFG (the paper's suggestion for SDXL-class models: "
-                        "0 15 -0.5); NORM_THRESHOLD <= 0 switches the clipping off; needs --guidance_rescale 0; default off")
-    parser.add_argument("--apg_space", type=str, default=argparse.SUPPRESS, choices=("x0", "model"), help="where APG projects: "
-                        "x0 = the denoised prediction (default, the paper), model = the raw output (diffusers)")
-    # likewise the three token-downsampling flags (token_downsampling_from_args)
-    parser.add_argument("--token_downsampling", type=int, default=argparse.SUPPRESS, choices=tuple(range(2, 9)), metavar="FACTOR",
-                        help="K/V token downsampling (ToDo) in the spatial self-attentions: keys and values from the tokens "
-                        "subsampled by FACTOR (2..8) per axis; default off")
-    parser.add_argument("--token_downsampling_levels", type=int, nargs="+", default=argparse.SUPPRESS, metavar="L",
-                        help="resolution levels it acts on (0 = the latent's own resolution; default 0)")
-    parser.add_argument("--token_downsampling_mode", type=str, default=argparse.SUPPRESS, choices=("nearest", "mean"),
-                        help="nearest = every FACTOR-th token (default, the paper), mean = the average of each FACTOR x FACTOR cell")
+    options.add_option_arguments(parser)
     return parser
 
 
-def token_downsampling_from_args(args):
-    """--token_downsampling FACTOR / --token_downsampling_levels / --token_downsampling_mode as the `token_downsampling=` dict
-    of image_guided_synthesis, or None. The two secondary flags without FACTOR are an error, not a silent no-op."""
-    f = getattr(args, "token_downsampling", None)
-    if f is None:
-        given = [k for k in ("token_downsampling_levels", "token_downsampling_mode") if hasattr(args, k)]
-        if given:
-            raise ValueError(f"--{given[0]} needs --token_downsampling FACTOR")
-        return None
-    return dict(factor=f, levels=tuple(getattr(args, "token_downsampling_levels", (0,))),
-                mode=getattr(args, "token_downsampling_mode", "nearest"))
-
-
-def apg_from_args(args):
-    """--apg ETA NORM_THRESHOLD MOMENTUM / --apg_space as the `apg=` dict of image_guided_synthesis, or None."""
-    v = getattr(args, "apg", None)
-    if v is None:
-        return None
-    return dict(eta=v[0], norm_threshold=v[1] if v[1] > 0 else None, momentum=v[2], space=getattr(args, "apg_space", "x0"))
-
-
-def freeu_from_args(args):
-    """--freeu S1 S2 B1 B2 / --freeu_version as the `freeu=` dict of image_guided_synthesis, or None."""
-    v = getattr(args, "freeu", None)
-    if v is None:
-        return None
-    return dict(s1=v[0], s2=v[1], b1=v[2], b2=v[3], version=getattr(args, "freeu_version", 1))
+# one lookup per option of samplers/options.py: its flags in a parsed namespace as the keyword's dict, or None
+freeu_from_args = functools.partial(options.from_args, "freeu")
+apg_from_args = functools.partial(options.from_args, "apg")
+token_downsampling_from_args = functools.partial(options.from_args, "token_downsampling")
 
 
 def seed_everything(seed):

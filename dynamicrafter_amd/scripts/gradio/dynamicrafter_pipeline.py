@@ -7,6 +7,7 @@ import os
 import numpy as np
 import torch
 
+from ...lvdm.models.samplers import options
 from ...lvdm.models.samplers.ddim import DDIMSampler
 from ..evaluation.funcs import get_latent_z, save_videos
 from ..evaluation.inference import resize_center_crop_f32
@@ -180,20 +181,16 @@ class DynamiCrafterImg2VideoPipeline:
         raise ValueError(f"output_type must be 'tensor', 'numpy' or 'pil', got {output_type!r}")
 
     @torch.no_grad()
+    @options.documented
     def __call__(self, image, prompt="", negative_prompt=None, num_inference_steps=50, guidance_scale=7.5, eta=0.0,
                  frame_stride=3, num_frames=None, height=None, width=None, num_videos_per_prompt=1, generator=None,
                  latents=None, output_type="tensor", return_dict=True, callback=None, callback_steps=1,
-                 cross_attention_kwargs=None, apg=None, token_downsampling=None, **kwargs):
+                 cross_attention_kwargs=None, freeu=None, apg=None, token_downsampling=None, **kwargs):
         """:398-530. Returns {"videos": v} (or v with return_dict=False); v is [b, 3, num_frames, height, width] as a device
         tensor ("tensor"), an ndarray ("numpy") or b lists of PIL frames ("pil"). Extra **kwargs reach DDIMSampler.sample.
-        `apg` (not in the reference): dict(eta=0.0, norm_threshold=None, momentum=0.0, space="x0") for adaptive projected
-        guidance in place of plain CFG (DDIMSampler.sample's `apg=`); needs guidance_scale != 1.
-        `token_downsampling` (not in the reference): dict(factor=2, levels=(0,), mode="nearest") for K/V token downsampling in
-        the spatial self-attentions during this call only (DDIMSampler.sample's `token_downsampling=`)."""
-        if apg is not None:
-            kwargs["apg"] = apg
-        if token_downsampling is not None:
-            kwargs["token_downsampling"] = token_downsampling
+        `freeu` and `token_downsampling` below hold for this call only; enable_freeu / enable_token_downsampling set them for
+        every later call."""
+        options.fold(kwargs, freeu=freeu, apg=apg, token_downsampling=token_downsampling)
         if isinstance(prompt, str):
             prompt = [prompt]
         batch_size = len(prompt)

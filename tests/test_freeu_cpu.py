@@ -184,8 +184,10 @@ def _check(net, seen):
 
 
 def test_samplers_restore_after_a_raise(spied):
-    from dynamicrafter_amd.lvdm.models.samplers.ddim import DDIMSampler, freeu_scope
+    from dynamicrafter_amd.lvdm.models.samplers.ddim import DDIMSampler
     from dynamicrafter_amd.lvdm.models.samplers.dpm_solver import DPMSolverSampler
+    from dynamicrafter_amd.lvdm.models.samplers.options import model_settings_scope
+    freeu_scope = lambda model, cfg: model_settings_scope(model, dict(freeu=cfg))
     model, seen = spied
     net = model.model.diffusion_model
     x = torch.zeros(SHAPE)

@@ -260,7 +260,8 @@ def _check(net, seen):
 
 
 def test_scope_helper(spied):
-    from dynamicrafter_amd.lvdm.models.samplers.ddim import token_downsampling_scope
+    from dynamicrafter_amd.lvdm.models.samplers.options import model_settings_scope
+    token_downsampling_scope = lambda model, cfg: model_settings_scope(model, dict(token_downsampling=cfg))
     model, seen = spied
     net = model.model.diffusion_model
     with token_downsampling_scope(model, TODO):

@@ -16,14 +16,11 @@ and --merge RESULT --parent_json FILES adds the JSON lines those runs printed to
 Prints one JSON object (and writes it to --out)."""
 import argparse
 import json
-import os
-import sys
-import time
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import step_ab
+
 SETTING = dict(eta=0.0, norm_threshold=15.0, momentum=-0.5)
 
 
@@ -48,33 +45,13 @@ def main():
                                        kernel_source_hash=d["kernel_source_hash"], host=d["host"]))
     if parent:
         out["parent_off"] = parent
-    line = json.dumps(out)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    step_ab.emit(out, args.out)
 
 
 def measure(args):
-    import bench
     from dynamicrafter_amd import ops
-    from dynamicrafter_amd.lvdm.models.samplers.ddim import DDIMSampler, FusedRun
-    dev = torch.device("cuda:0")
-    bench.log(f"building inference_{args.res} model (random init)")
-    model, _ = bench.build_model(args.res, dev)
-    inp = {k: v.to(dev) for k, v in bench.make_clip_inputs(args.res, 1).items()}
-    cond = {"c_crossattn": [inp["cond_ctx"]], "c_concat": [inp["c_concat"]]}
-    uc = {"c_crossattn": [inp["uc_ctx"]], "c_concat": [inp["c_concat"]]}
-    x_T = inp["x_T"].float().contiguous()
-    S, n = bench.S_STEPS, args.n
-    noises = torch.randn((S,) + tuple(x_T.shape), generator=torch.Generator().manual_seed(100)).to(dev)
-    s = DDIMSampler(model)
-    s.make_schedule(S, ddim_discretize="uniform_trailing", ddim_eta=1.0, verbose=False)
-
-    def new_run(**kw):
-        return FusedRun(s, x_T.clone(), [cond, uc], fs=inp["fs"], noises=noises, cfg_scale=7.5, **kw)
-
+    c = step_ab.setup(args.res)
+    bench, x_T, new_run = c.bench, c.x_T, c.new_run
     runs = {"off": new_run(guidance_rescale=0.7).capture()}
     if not args.off_only:
         runs["off_plain"] = new_run().capture()
@@ -82,28 +59,9 @@ def measure(args):
         runs["apg_model"] = new_run(apg=dict(SETTING, space="model")).capture()
     bench.log("runs captured")
 
-    def timed(run):
-        run.rewind(x_T)
-        t0 = time.perf_counter()
-        for _ in range(n):
-            run.step()
-        run.sync()
-        return (time.perf_counter() - t0) * 1e3 / n
-
-    for r in runs.values():
-        timed(r)
-    per = {k: [] for k in runs}
-    for b in range(args.blocks):
-        for k, r in runs.items():
-            per[k].append(timed(r))
-        bench.log(f"block {b + 1} of {args.blocks}")
-    med = {k: sorted(v)[len(v) // 2] for k, v in per.items()}
-    out = dict(res=args.res, latent=list(x_T.shape), branches=2, steps_per_block=n, blocks=args.blocks,
-               ms_per_step_blocks={k: [round(x, 3) for x in v] for k, v in per.items()},
-               ms_per_step_median={k: round(v, 3) for k, v in med.items()},
-               ms_per_step_range={k: [round(min(v), 3), round(max(v), 3)] for k, v in per.items()},
-               finite={k: bool(torch.isfinite(r.img).all().item()) for k, r in runs.items()},
-               kernel_source_hash=bench.kernel_source_hash(), device=torch.cuda.get_device_name(0), host=os.uname().nodename)
+    per, med = step_ab.alternate({k: (lambda r=r: step_ab.timed(r, x_T, args.n)) for k, r in runs.items()}, args.blocks, bench.log)
+    out = dict(res=args.res, latent=list(x_T.shape), branches=2, steps_per_block=args.n, blocks=args.blocks,
+               **step_ab.timing_fields(per, med), finite=step_ab.finite(runs), **step_ab.header(bench))
     if not args.off_only:
         out["setting"] = SETTING
         out["minus_off_ms"] = {k: round(med[k] - med["off"], 3) for k in med if k != "off"}

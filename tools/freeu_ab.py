@@ -13,16 +13,12 @@ read twice and written once, the first half of h read and written once; version 
 --off_only times the off run alone: the same script runs in a checkout of the parent commit for the same-session comparison.
 Prints one JSON object (and writes it to --out)."""
 import argparse
-import json
-import os
 import re
-import sys
-import time
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import step_ab
+
 SETTING = dict(s1=0.9, s2=0.2, b1=1.4, b2=1.6)
 
 
@@ -40,24 +36,10 @@ def main():
     ap.add_argument("--out", default=None)
     ap.add_argument("--off_only", action="store_true")
     args = ap.parse_args()
-    import bench
     from dynamicrafter_amd import ops
-    from dynamicrafter_amd.lvdm.models.samplers.ddim import DDIMSampler, FusedRun
-    dev = torch.device("cuda:0")
-    bench.log(f"building inference_{args.res} model (random init)")
-    model, _ = bench.build_model(args.res, dev)
-    net = model.model.diffusion_model
-    inp = {k: v.to(dev) for k, v in bench.make_clip_inputs(args.res, 1).items()}
-    cond = {"c_crossattn": [inp["cond_ctx"]], "c_concat": [inp["c_concat"]]}
-    uc = {"c_crossattn": [inp["uc_ctx"]], "c_concat": [inp["c_concat"]]}
-    x_T = inp["x_T"].float().contiguous()
-    S, n = bench.S_STEPS, args.n
-    noises = torch.randn((S,) + tuple(x_T.shape), generator=torch.Generator().manual_seed(100)).to(dev)
-    s = DDIMSampler(model)
-    s.make_schedule(S, ddim_discretize="uniform_trailing", ddim_eta=1.0, verbose=False)
-
-    def new_run():
-        return FusedRun(s, x_T.clone(), [cond, uc], fs=inp["fs"], noises=noises, cfg_scale=7.5, guidance_rescale=0.7)
+    c = step_ab.setup(args.res)
+    bench, model, net, x_T = c.bench, c.model, c.net, c.x_T
+    new_run = lambda: c.new_run(guidance_rescale=0.7)
 
     runs = {"off": new_run().capture()}
     versions = () if args.off_only else (1, 2)
@@ -68,28 +50,9 @@ def main():
         net.disable_freeu()
     bench.log("runs captured")
 
-    def timed(run):
-        run.rewind(x_T)
-        t0 = time.perf_counter()
-        for _ in range(n):
-            run.step()
-        run.sync()
-        return (time.perf_counter() - t0) * 1e3 / n
-
-    for r in runs.values():
-        timed(r)
-    per = {k: [] for k in runs}
-    for b in range(args.blocks):
-        for k, r in runs.items():
-            per[k].append(timed(r))
-        bench.log(f"block {b + 1} of {args.blocks}")
-    med = {k: sorted(v)[len(v) // 2] for k, v in per.items()}
-    out = dict(res=args.res, latent=list(x_T.shape), branches=2, steps_per_block=n, blocks=args.blocks,
-               ms_per_step_blocks={k: [round(x, 3) for x in v] for k, v in per.items()},
-               ms_per_step_median={k: round(v, 3) for k, v in med.items()},
-               ms_per_step_range={k: [round(min(v), 3), round(max(v), 3)] for k, v in per.items()},
-               finite={k: bool(torch.isfinite(r.img).all().item()) for k, r in runs.items()},
-               kernel_source_hash=bench.kernel_source_hash(), device=torch.cuda.get_device_name(0), host=os.uname().nodename)
+    per, med = step_ab.alternate({k: (lambda r=r: step_ab.timed(r, x_T, args.n)) for k, r in runs.items()}, args.blocks, bench.log)
+    out = dict(res=args.res, latent=list(x_T.shape), branches=2, steps_per_block=args.n, blocks=args.blocks,
+               **step_ab.timing_fields(per, med), finite=step_ab.finite(runs), **step_ab.header(bench))
     if versions:
         out["setting"] = SETTING
         out["on_minus_off_ms"] = {k: round(med[k] - med["off"], 3) for k in med if k != "off"}
@@ -128,12 +91,7 @@ def main():
         net.disable_freeu()
         out["freeu_launches"] = launches
         out["freeu_traffic"] = bound
-    line = json.dumps(out)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    step_ab.emit(out, args.out)
 
 
 if __name__ == "__main__":

@@ -6,15 +6,10 @@ Both runs share the model and the conditioning; their captured steps are replaye
 launches (HIP events on the graph stream), so clock drift hits both alike. Prints one JSON object (and writes it to
 --out)."""
 import argparse
-import ctypes as C
-import json
-import os
-import sys
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import step_ab
 
 
 def main():
@@ -24,56 +19,19 @@ def main():
     ap.add_argument("--blocks", type=int, default=4)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    import bench
-    from dynamicrafter_amd import _hip, ops
-    from dynamicrafter_amd.lvdm.models.samplers.ddim import DDIMSampler, FusedRun
+    from dynamicrafter_amd import ops
     from dynamicrafter_amd.lvdm.models.samplers.dpm_solver import DPMSolverSampler, DpmRun
-    l = _hip.lib()
-    dev = torch.device("cuda:0")
-    bench.log(f"building inference_{args.res} model (random init)")
-    model, _ = bench.build_model(args.res, dev)
-    inp = {k: v.to(dev) for k, v in bench.make_clip_inputs(args.res, 1).items()}
-    cond = {"c_crossattn": [inp["cond_ctx"]], "c_concat": [inp["c_concat"]]}
-    uc = {"c_crossattn": [inp["uc_ctx"]], "c_concat": [inp["c_concat"]]}
-    x_T = inp["x_T"].float().contiguous()
-    S = bench.S_STEPS
-    noises = torch.randn((S,) + tuple(x_T.shape), generator=torch.Generator().manual_seed(100)).to(dev)
-    runs = {}
-    for name in ("ddim", "dpmpp_2m_sde"):
-        if name == "ddim":
-            s = DDIMSampler(model)
-            s.make_schedule(S, ddim_discretize="uniform_trailing", ddim_eta=1.0, verbose=False)
-            cls = FusedRun
-        else:
-            s = DPMSolverSampler(model, solver=name)
-            s.make_schedule(S, ddim_discretize="uniform_trailing", verbose=False)
-            cls = DpmRun
-        runs[name] = cls(s, x_T.clone(), [cond, uc], fs=inp["fs"], noises=noises, cfg_scale=7.5,
-                         guidance_rescale=0.7).capture()
-
-    def timed(run, n):
-        run.rewind(x_T)
-        e0, e1 = C.c_void_p(), C.c_void_p()
-        l.dc_event_create(C.byref(e0)); l.dc_event_create(C.byref(e1))
-        l.dc_event_record(e0, run.graph._stream)
-        for _ in range(n):
-            run.step()
-        l.dc_event_record(e1, run.graph._stream)
-        run.sync()
-        ms = C.c_float()
-        l.dc_event_elapsed_ms(e0, e1, C.byref(ms))
-        l.dc_event_destroy(e0); l.dc_event_destroy(e1)
-        return ms.value / n
-
+    c = step_ab.setup(args.res)
+    bench, dev, x_T, noises = c.bench, c.dev, c.x_T, c.noises
+    dpm = DPMSolverSampler(c.model, solver="dpmpp_2m_sde")
+    dpm.make_schedule(c.S, ddim_discretize="uniform_trailing", verbose=False)
+    runs = {"ddim": c.new_run(guidance_rescale=0.7).capture(),
+            "dpmpp_2m_sde": DpmRun(dpm, x_T.clone(), [c.cond, c.uc], fs=c.inp["fs"], noises=noises, cfg_scale=7.5,
+                                   guidance_rescale=0.7).capture()}
     bench.log("both steps captured")
-    for run in runs.values():                                  # warm-up
-        timed(run, 3)
-    per = {k: [] for k in runs}
-    for _ in range(args.blocks):
-        for k, run in runs.items():
-            per[k].append(timed(run, args.steps))
+    per, med = step_ab.alternate({k: (lambda r=r: step_ab.timed_events(r, x_T, args.steps)) for k, r in runs.items()}, args.blocks)
     bench.log(f"timed {args.blocks} x {args.steps} steps of each")
-    finite = {k: bool(torch.isfinite(r.img).all().item()) for k, r in runs.items()}
+    finite = step_ab.finite(runs)
 
     # the update kernels alone, eager on the current stream: 2 branches as channels-last rows, guidance rescale on
     B, Cc = x_T.shape[0], x_T.shape[1]
@@ -99,20 +57,11 @@ def main():
         b.record()
         torch.cuda.synchronize()
         kern_us[k] = a.elapsed_time(b) / 200 * 1e3
-    med = {k: sorted(v)[len(v) // 2] for k, v in per.items()}
-    out = dict(res=args.res, steps_per_block=args.steps, blocks=args.blocks,
-               ms_per_step_blocks={k: [round(x, 3) for x in v] for k, v in per.items()},
-               ms_per_step_median={k: round(v, 3) for k, v in med.items()},
+    out = dict(res=args.res, steps_per_block=args.steps, blocks=args.blocks, **step_ab.timing_fields(per, med, ranges=False),
                dpm_minus_ddim_ms=round(med["dpmpp_2m_sde"] - med["ddim"], 3),
                update_kernels_us={k: round(v, 1) for k, v in kern_us.items()},
-               finite=finite, kernel_source_hash=bench.kernel_source_hash(),
-               device=torch.cuda.get_device_name(0))
-    line = json.dumps(out)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+               finite=finite, **step_ab.header(bench, host=False))
+    step_ab.emit(out, args.out)
 
 
 if __name__ == "__main__":

@@ -17,15 +17,11 @@ projection) and the GEMM that projects kv - so that what the attention saves sta
 parent for the same-job comparison. Prints one JSON object (and writes it to --out)."""
 import argparse
 import ctypes as C
-import json
-import os
-import sys
-import time
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import step_ab
+
 SETTINGS = {"f2_l0": dict(factor=2, levels=(0,)), "f2_l01": dict(factor=2, levels=(0, 1)), "f4_l0": dict(factor=4, levels=(0,))}
 WATCHED = ("flash_attn_d64(self)", "ln_pool_tokens", "ln_linear")
 
@@ -54,22 +50,9 @@ def traced_rows(ops, _hip, fn, watch_gemm):
 
 
 def one_config(res, args, bench, ops, _hip):
-    from dynamicrafter_amd.lvdm.models.samplers.ddim import DDIMSampler, FusedRun
-    dev = torch.device("cuda:0")
-    bench.log(f"building inference_{res} model (random init)")
-    model, _ = bench.build_model(res, dev)
-    net = model.model.diffusion_model
-    inp = {k: v.to(dev) for k, v in bench.make_clip_inputs(res, 1).items()}
-    cond = {"c_crossattn": [inp["cond_ctx"]], "c_concat": [inp["c_concat"]]}
-    uc = {"c_crossattn": [inp["uc_ctx"]], "c_concat": [inp["c_concat"]]}
-    x_T = inp["x_T"].float().contiguous()
-    S, n = bench.S_STEPS, args.n
-    noises = torch.randn((S,) + tuple(x_T.shape), generator=torch.Generator().manual_seed(100)).to(dev)
-    s = DDIMSampler(model)
-    s.make_schedule(S, ddim_discretize="uniform_trailing", ddim_eta=1.0, verbose=False)
-
-    def new_run():
-        return FusedRun(s, x_T.clone(), [cond, uc], fs=inp["fs"], noises=noises, cfg_scale=7.5, guidance_rescale=0.7)
+    c = step_ab.setup(res)
+    model, net, x_T = c.model, c.net, c.x_T
+    new_run = lambda: c.new_run(guidance_rescale=0.7)
 
     runs = {"off": new_run().capture()}
     settings = {} if args.off_only else {k: dict(v, mode="mean" if args.mean else "nearest") for k, v in SETTINGS.items()}
@@ -80,27 +63,9 @@ def one_config(res, args, bench, ops, _hip):
         net.disable_token_downsampling()
     bench.log("runs captured")
 
-    def timed(run):
-        run.rewind(x_T)
-        t0 = time.perf_counter()
-        for _ in range(n):
-            run.step()
-        run.sync()
-        return (time.perf_counter() - t0) * 1e3 / n
-
-    for r in runs.values():
-        timed(r)
-    per = {k: [] for k in runs}
-    for b in range(args.blocks):
-        for k, r in runs.items():
-            per[k].append(timed(r))
-        bench.log(f"block {b + 1} of {args.blocks}")
-    med = {k: sorted(v)[len(v) // 2] for k, v in per.items()}
-    out = dict(latent=list(x_T.shape), branches=2, steps_per_block=n, blocks=args.blocks,
-               ms_per_step_blocks={k: [round(x, 3) for x in v] for k, v in per.items()},
-               ms_per_step_median={k: round(v, 3) for k, v in med.items()},
-               ms_per_step_range={k: [round(min(v), 3), round(max(v), 3)] for k, v in per.items()},
-               finite={k: bool(torch.isfinite(r.img).all().item()) for k, r in runs.items()})
+    per, med = step_ab.alternate({k: (lambda r=r: step_ab.timed(r, x_T, args.n)) for k, r in runs.items()}, args.blocks, bench.log)
+    out = dict(latent=list(x_T.shape), branches=2, steps_per_block=args.n, blocks=args.blocks,
+               **step_ab.timing_fields(per, med), finite=step_ab.finite(runs))
     if settings:
         out["settings"] = {k: dict(v, levels=list(v["levels"])) for k, v in settings.items()}
         out["on_minus_off_ms"] = {k: round(med[k] - med["off"], 3) for k in med if k != "off"}
@@ -142,15 +107,9 @@ def main():
     args = ap.parse_args()
     import bench
     from dynamicrafter_amd import _hip, ops
-    out = dict(mode="off only" if args.off_only else "mean" if args.mean else "nearest",
-               kernel_source_hash=bench.kernel_source_hash(), device=torch.cuda.get_device_name(0), host=os.uname().nodename,
+    out = dict(mode="off only" if args.off_only else "mean" if args.mean else "nearest", **step_ab.header(bench),
                configs={res: one_config(res, args, bench, ops, _hip) for res in args.res})
-    line = json.dumps(out)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+    step_ab.emit(out, args.out)
 
 
 if __name__ == "__main__":

@@ -17,7 +17,6 @@ The default `python bench.py` runs, parent and new alternately, are not made her
 two trees, run by hand in the same job (profiles/README.md gives the commands next to the recorded results).
 Prints one JSON object (and writes it to --out)."""
 import argparse
-import ctypes as C
 import json
 import os
 import subprocess
@@ -25,8 +24,7 @@ import sys
 
 import torch
 
-ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-sys.path.insert(0, ROOT)
+import step_ab
 
 
 def parent_plain_blocks(tree, res, steps, blocks):
@@ -62,10 +60,9 @@ def main():
         blk, parent_hash = parent_plain_blocks(os.path.abspath(args.parent_tree), args.res, args.steps, args.blocks)
         parent += blk
     import bench
-    from dynamicrafter_amd import _hip, ops
+    from dynamicrafter_amd import ops
     from dynamicrafter_amd.lvdm.models.samplers.ddim import DDIMSampler, FusedRun, windowed
     from dynamicrafter_amd.lvdm.models.samplers.windows import window_plan
-    l = _hip.lib()
     dev = torch.device("cuda:0")
     bench.log(f"building inference_{args.res} model (random init)")
     model, _ = bench.build_model(args.res, dev)
@@ -96,30 +93,10 @@ def main():
     W, n_w = wr.plan["W"], wr.prep["win"]["n_w"]
     W_real = window_plan(TL, T, args.stride, "triangle", args.shift, S)[0].shape[1]
 
-    def timed(name, n):
-        run = runs[name]
-        run.rewind(x_T[name])
-        e0, e1 = C.c_void_p(), C.c_void_p()
-        l.dc_event_create(C.byref(e0)); l.dc_event_create(C.byref(e1))
-        l.dc_event_record(e0, run.graph._stream)
-        for _ in range(n):
-            run.step()
-        l.dc_event_record(e1, run.graph._stream)
-        run.sync()
-        ms = C.c_float()
-        l.dc_event_elapsed_ms(e0, e1, C.byref(ms))
-        l.dc_event_destroy(e0); l.dc_event_destroy(e1)
-        return ms.value / n
-
     bench.log(f"both steps captured: W = {W_real} windows ({W} with padding), {n_w} per UNet call")
-    for name in runs:                                           # warm-up
-        timed(name, 2)
-    per = {k: [] for k in runs}
-    for _ in range(args.blocks):
-        for k in runs:
-            per[k].append(timed(k, args.steps))
+    per, med = step_ab.alternate({k: (lambda k=k: step_ab.timed_events(runs[k], x_T[k], args.steps)) for k in runs}, args.blocks)
     bench.log(f"timed {args.blocks} x {args.steps} steps of each")
-    finite = {k: bool(torch.isfinite(r.img).all().item()) for k, r in runs.items()}
+    finite = step_ab.finite(runs)
     if args.parent_tree:                                        # and after, with this process idle
         parent += parent_plain_blocks(os.path.abspath(args.parent_tree), args.res, args.steps, args.blocks)[0]
         bench.log(f"parent tree's plain step: {len(parent)} blocks in two fresh processes")
@@ -160,12 +137,10 @@ def main():
         torch.cuda.synchronize()
         us = a.elapsed_time(b) / 100 * 1e3
         kern_us[k] = dict(us=round(us, 1), mbytes=round(nbytes / 1e6, 2), gbs=round(nbytes / us / 1e3, 1))
-    med = {k: sorted(v)[len(v) // 2] for k, v in per.items()}
     out = dict(res=args.res, frames=TL, window=T, stride=args.stride, shift=args.shift, windows=W_real, windows_padded=W,
                windows_per_call=n_w, max_windows_per_call=model.max_windows_per_call(tuple(xl.shape), 2, T),
                steps_per_block=args.steps, blocks=args.blocks,
-               ms_per_step_blocks={k: [round(x, 3) for x in v] for k, v in per.items()},
-               ms_per_step_median={k: round(v, 3) for k, v in med.items()},
+               **step_ab.timing_fields(per, med, ranges=False),
                ratio_windowed_over_W_plain=round(med["windowed"] / (W_real * med["plain"]), 4),
                parent_plain_ms_per_step_blocks=[round(x, 3) for x in parent] or None,
                parent_plain_ms_per_step_median=round(sorted(parent)[len(parent) // 2], 3) if parent else None,
@@ -173,13 +148,8 @@ def main():
                                                    if parent else None),
                parent_kernel_source_hash=parent_hash,
                kernels=kern_us, unet_scratch_mbytes={k: round(v / 1e6, 1) for k, v in scratch.items()},
-               finite=finite, kernel_source_hash=bench.kernel_source_hash(), device=torch.cuda.get_device_name(0))
-    line = json.dumps(out)
-    print(line)
-    if args.out:
-        os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
-        with open(args.out, "w") as f:
-            f.write(line + "\n")
+               finite=finite, **step_ab.header(bench, host=False))
+    step_ab.emit(out, args.out)
 
 
 if __name__ == "__main__":
