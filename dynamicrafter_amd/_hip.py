@@ -116,6 +116,8 @@ SIGNATURES = {
     "dc_pack_latent": (_I, [_P, _P, _P, _I, _I, _I, _I, _I, _I, _I, _P]),
     "dc_pack_latent_windows": (_I, [_P, _P, _P, _P, _P] + [_I] * 13 + [_P]),
     "dc_window_merge": (_I, [_P, _I, _P, _I, _P, _P, _P] + [_I] * 12 + [_P]),
+    "dc_pack_latent_tiles": (_I, [_P, _P, _P, _P, _P] + [_I] * 16 + [_P]),
+    "dc_tile_merge": (_I, [_P, _I, _P, _I, _P, _P, _P] + [_I] * 15 + [_P]),
     "dc_nchw_to_rows": (_I, [_P, _P, _I, _I, _I, _I, _F, _P]),
     "dc_rows_to_nchw": (_I, [_P, _I, _I, _P, _I, _I, _I, _F, _P]),
     "dc_im2col3x3_c8": (_I, [_P, _I, _P, _I, _I, _I, _I, _P]),

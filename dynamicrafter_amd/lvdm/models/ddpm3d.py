@@ -285,19 +285,26 @@ class LatentDiffusion(DDPM):
         return out[0] if isinstance(out, tuple) else out
 
     # ------------------------------------------------------------------ MI355X fast path
-    def prepare_branches(self, x_shape, branches, fs=None, windows=None):
+    def prepare_branches(self, x_shape, branches, fs=None, windows=None, tiles=None):
         """Step-invariant part of a guided UNet evaluation: per-frame context rows of every conditioning branch
         (cond / uncond [/ image-only]), their c_concat tensors and the fs table. Done once per sampler call,
         outside the per-step (graph-captured) region; allocates.
         windows = dict(T=, n_w=) (apply_model_windows): x_shape is the long clip's, one UNet call takes n_w windows of
         T frames of each of the B clips, so the context rows and the fs entry of clip b are repeated for its n_w
-        windows (frame j of every window reads image-token set j); c_concat stays T_long frames long."""
+        windows (frame j of every window reads image-token set j); c_concat stays T_long frames long.
+        tiles = dict(T=, h=, w=, n_w=) (apply_model_tiles): the same for n_w boxes of T x h x w inside the long latent;
+        c_concat stays at the long size."""
         net = self.model.diffusion_model
         key = self.model.conditioning_key
         B, Cx, T, H, W = x_shape
         n_w = 1
+        if windows is not None and tiles is not None:
+            raise ValueError("prepare_branches: windows= and tiles= are two forms of one thing; a tiled time axis is tiles=")
         if windows is not None:
             T, n_w = int(windows["T"]), int(windows["n_w"])
+        if tiles is not None:
+            T, n_w = int(tiles["T"]), int(tiles["n_w"])
+            windows = tiles                             # below: whatever repeats per box repeats as it does per window
         dev = self.device
         nb = len(branches)
         ccs, ctx_all, Lc = [], None, None
@@ -332,7 +339,8 @@ class LatentDiffusion(DDPM):
         # once per sampler call, instead of in every UNet forward of every step
         ctx_kv = net.precompute_context_kv(ctx_all) if os.environ.get("DC_HOIST_CTX_KV", "1") != "0" else None
         return dict(nb=nb, ccs=ccs, ctx_all=ctx_all, Lc=Lc, fs_table=fs_table, shape=tuple(x_shape), share=share,
-                    ctx_kv=ctx_kv, win=None if windows is None else dict(T=T, n_w=n_w))
+                    ctx_kv=ctx_kv, win=None if windows is None or tiles is not None else dict(T=T, n_w=n_w),
+                    tile=None if tiles is None else dict(T=T, h=int(tiles["h"]), w=int(tiles["w"]), n_w=n_w))
 
     def apply_model_rows(self, x, prep, t_table, t_index=None):
         """All branches of `prep` on the same latent x as ONE batched UNet forward (kernel launches only; safe
@@ -351,10 +359,13 @@ class LatentDiffusion(DDPM):
                                 fs_table=prep["fs_table"], t_index=t_index, shared_prefix=prep.get("share", 1),
                                 ctx_kv=prep.get("ctx_kv"))
 
-    def max_windows_per_call(self, x_shape, nb, T):
+    def max_windows_per_call(self, x_shape, nb, T, hw=None):
         """The most T-frame windows of a [B, C, T_long, h, w] latent one batched UNet call can take with nb branches:
-        every scratch buffer of the forward must stay under 2^31 elements (rows x row stride)."""
+        every scratch buffer of the forward must stay under 2^31 elements (rows x row stride). `hw`: the
+        (height, width) of one box when the call takes spatial tiles of the latent (default: the latent's own)."""
         B, _, _, H, W = x_shape
+        if hw is not None:
+            H, W = (int(v) for v in hw)
         net = self.model.diffusion_model
         # per clip: the widest activation buffer, and the context rows (at most 77 + 16 tokens per frame) with their
         # widest projection, which outgrow the activations on a latent of fewer than ~100 positions
@@ -388,6 +399,33 @@ class LatentDiffusion(DDPM):
                                  ctx_kv=prep.get("ctx_kv"))
             ops.window_merge(e, out, plan, nb=nb, B=B, C=net.out_channels, HW=H * W, w0=w0, n_w=n_w, index=index,
                              step_index=t_index, accumulate=w0 > 0)
+        return out
+
+    def apply_model_tiles(self, x, prep, t_table, plan, out, t_index=None, index=0):
+        """apply_model_windows for boxes in space (and time): x fp32 [B, 4, T_long, H_long, W_long], the UNet runs on the
+        boxes of the current step of `plan` (ops.tile_tables), prep["tile"]["n_w"] of them per call with
+        B_eff = nb * B * n_w at the box's T, h, w, and each call's output is blended into `out` before the next call
+        reuses the arena's output buffer. t_table int64 [n_steps, nb * B * n_w]. Kernel launches only. Returns `out`:
+        fp32 rows [nb * B * T_long * H_long * W_long, C], branch-major."""
+        net = self.model.diffusion_model
+        B, Cx, TL, HL, WL = prep["shape"]
+        nb, tile = prep["nb"], prep["tile"]
+        T, H, W, n_w = tile["T"], tile["h"], tile["w"], tile["n_w"]
+        if plan["W"] % n_w or plan["box_shape"] != (T, H, W) or plan["long_shape"] != (TL, HL, WL):
+            raise ValueError(f"tile plan (W {plan['W']}, boxes {plan['box_shape']} in {plan['long_shape']}) does not fit "
+                             f"calls of {n_w} boxes of {(T, H, W)} in {(TL, HL, WL)}")
+        Mc = B * n_w * T * H * W
+        xr = net._arena.get("x_rows", nb * Mc, C_IN_PAD, device=x.device)
+        Lc = prep["Lc"]
+        for w0 in range(0, plan["W"], n_w):
+            for k, cc in enumerate(prep["ccs"]):
+                ops.pack_latent_tiles(x, cc, xr[k * Mc:(k + 1) * Mc], plan, B=B, Cx=Cx, Cc=0 if cc is None else cc.shape[1],
+                                      w0=w0, n_w=n_w, index=index, step_index=t_index)
+            e = net.forward_rows(xr, t_table, prep["ctx_all"], B=nb * B * n_w, T=T, H=H, W=W, Lc=Lc, n_text=min(77, Lc),
+                                 fs_table=prep["fs_table"], t_index=t_index, shared_prefix=prep.get("share", 1),
+                                 ctx_kv=prep.get("ctx_kv"))
+            ops.tile_merge(e, out, plan, nb=nb, B=B, C=net.out_channels, w0=w0, n_w=n_w, index=index, step_index=t_index,
+                           accumulate=w0 > 0)
         return out
 
 

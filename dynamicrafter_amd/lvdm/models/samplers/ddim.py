@@ -35,17 +35,22 @@ from .... import _hip, ops
 from ..utils_diffusion import make_ddim_sampling_parameters, make_ddim_timesteps
 from . import options
 from .options import OPTIONS, takes_model_settings
+from .tiles import box_weights, check_box, pad_tiles, tile_plan, tiles_config
 from .windows import pad_plan, window_plan, windows_per_call
 
 
-def _step_inputs(img, S, noises, mask, x0, q_noises, clean_cond, long_branches=None):
+def _step_inputs(img, S, noises, mask, x0, q_noises, clean_cond, long_branches=None, long_space=False):
     """The per-step draws and the mask operands as the kernels read them, checked in this one place for the fused and
     the generic path: fp32 on the latent's device, `noises` / `q_noises` long enough for S steps, x0 / mask expanded to
     the latent's shape. With windows (`long_branches`: the conditioning branches) everything is T_long frames long, the
-    c_concat entries included. Returns (noises, blend); blend is None without a mask."""
+    c_concat entries included; with tiles (`long_space`) they have the latent's height and width too. Returns
+    (noises, blend); blend is None without a mask."""
     f32 = lambda t: t.to(device=img.device, dtype=torch.float32)
     for k, c in enumerate(long_branches or ()):
         for cc in (c.get("c_concat") or ()) if isinstance(c, dict) else ():
+            if long_space and (cc.dim() != img.dim() or tuple(cc.shape[2:]) != tuple(img.shape[2:])):
+                raise ValueError(f"tiled sampling: c_concat of branch {k} has shape {tuple(cc.shape)}, the latent is "
+                                 f"{tuple(img.shape[2:])} (frames, height, width)")
             if cc.dim() != img.dim() or cc.shape[2] != img.shape[2]:
                 raise ValueError(f"windowed sampling: c_concat of branch {k} has shape {tuple(cc.shape)}, the latent has "
                                  f"{img.shape[2]} frames")
@@ -138,16 +143,19 @@ class StepRun:
     ending in ops.advance_counter), and `_reset_state()`, which puts back whatever else a step changes besides the
     latent and the counter. `step()` advances the device counter by one; after `S` steps `rewind()` starts over."""
 
-    def __init__(self, model, img, branches, t_table, fs=None, windows=None):
+    def __init__(self, model, img, branches, t_table, fs=None, windows=None, tiles=None):
         self.model, self.img = model, img
         self.S = int(t_table.shape[0])
         self.nb = len(branches)
         t_table = t_table.to(torch.int64)
-        if windows is None:
+        if windows is None and tiles is None:
             self.prep = model.prepare_branches(tuple(img.shape), branches, fs=fs)
-        else:                                           # the UNet batch is (branch, clip, window): WindowedRun
+        elif tiles is None:                             # the UNet batch is (branch, clip, window): WindowedRun
             self.prep = model.prepare_branches(tuple(img.shape), branches, fs=fs, windows=windows)
             t_table = t_table.repeat_interleave(int(windows["n_w"]), dim=1)
+        else:                                           # the UNet batch is (branch, clip, box): TiledRun
+            self.prep = model.prepare_branches(tuple(img.shape), branches, fs=fs, tiles=tiles)
+            t_table = t_table.repeat_interleave(int(tiles["n_w"]), dim=1)
         self.ws = ops.step_workspace(img.shape[0], img.device)
         self.counter = torch.zeros(1, dtype=torch.int32, device=img.device)
         self.t_table = t_table.repeat(1, self.nb).contiguous().to(img.device)   # [S, B] -> [S, nb*B]
@@ -210,7 +218,7 @@ class FusedRun(StepRun):
 
     def __init__(self, sampler, img, branches, *, fs=None, noises=None, cfg_scale=1.0, cfg_img=None,
                  guidance_rescale=0.0, temperature=1.0, mask=None, x0=None, q_noises=None, clean_cond=False,
-                 windows=None, last=None, apg=None):
+                 windows=None, tiles=None, last=None, apg=None):
         # `last`: a partial run over the last n steps of the schedule (decode, timesteps=): the execution-order tables and
         # the timestep table are sliced, so the counter still starts at 0 and noises / q_noises are [n, ...]
         S_all = int(sampler._exec_timesteps.shape[0])
@@ -219,16 +227,20 @@ class FusedRun(StepRun):
             raise ValueError(f"a partial run covers 1 .. {S_all} steps, got {n}")
         if n < S_all and windows is not None:
             raise ValueError("partial runs are not implemented with windows")
+        if n < S_all and tiles is not None:
+            raise ValueError("partial runs are not implemented with tiles")
         # `apg`: adaptive projected guidance (apg_config's dict) in place of the CFG combine: two launches between the UNet
         # and the unchanged update, which then sees the guided rows as a single branch
         apg = check_apg(apg, sampler, len(branches), guidance_rescale, cfg_img is not None, last=n)
         t_host = torch.as_tensor(sampler._exec_timesteps[S_all - n:].copy(), dtype=torch.int64)
-        super().__init__(sampler.model, img, branches, t_host[:, None].expand(-1, img.shape[0]), fs=fs, windows=windows)
+        super().__init__(sampler.model, img, branches, t_host[:, None].expand(-1, img.shape[0]), fs=fs, windows=windows,
+                         **({} if tiles is None else {"tiles": tiles}))
         self.sampler = sampler
         self.tables = sampler._tables if n == S_all else \
             {k: v[S_all - n:] for k, v in sampler._tables.items() if not k.startswith("inv_")}
         self.noises, self.blend = _step_inputs(img, self.S, noises, mask, x0, q_noises, clean_cond,
-                                               long_branches=None if windows is None else branches)
+                                               long_branches=None if windows is None and tiles is None else branches,
+                                               long_space=tiles is not None)
         self.pred_x0 = torch.empty_like(img)
         self.apg = apg
         if apg is None:
@@ -377,6 +389,86 @@ class _WindowedModel:
             seg.copy_((seg.double() + g.double().view(1, 1, T, 1, 1) * e.double()).float())
         return out
 
+
+class TiledRun:
+    """Mixin ahead of FusedRun or a subclass of it (`tiled(cls)`), WindowedRun's sibling in space: the latent is larger
+    than the box (T, h, w) one UNet call is made for, and the model evaluation of a step is, per chunk of `n_w` boxes, box
+    pack per branch + one batched UNet forward with B_eff = nb * B * n_w at the box's size + blend into the long output
+    rows (LatentDiffusion.apply_model_tiles). Mask blend, APG, the sampler's update (`_update`, unchanged, on
+    T_long * H_long * W_long positions, guidance-rescale statistics per clip over the whole latent), the counter and
+    capture / step / rewind / sync are the base run's. The box starts and the per-axis blend weights are two more device
+    tables indexed by the step counter (samplers/tiles.py), so one captured step graph serves boxes that move from step to
+    step. With a tiled time axis (`window_stride` beside `tiles`) the boxes are the product plan.
+
+    tile = dict(T=, h=, w=, stride=(st, sy, sx), weights=, shift=(dt, dy, dx), per_call=[, plan=]): per_call caps the boxes
+    of one UNet call (None: the most that keeps every scratch buffer under 2^31 elements); the plan is padded to whole
+    calls with weight-0 boxes."""
+
+    def __init__(self, sampler, img, branches, *, tile, **kw):
+        model = sampler.model
+        box_shape = (int(tile["T"]), int(tile["h"]), int(tile["w"]))
+        nb, S = len(branches), int(sampler._exec_timesteps.shape[0])
+        plan = tile.get("plan")                         # _denoise has built it already (argument checks)
+        if plan is None:
+            plan = tile_plan(tuple(img.shape[2:]), box_shape, tile["stride"], tile.get("weights", "triangle"),
+                             tile.get("shift", (0, 0, 0)), S)
+        W = plan[0].shape[1]
+        cap = model.max_windows_per_call(tuple(img.shape), nb, box_shape[0], hw=box_shape[1:])
+        n_w = windows_per_call(W, cap, tile.get("per_call"))
+        box, g = pad_tiles(*plan, n_w)
+        super().__init__(sampler, img, branches, tiles=dict(T=box_shape[0], h=box_shape[1], w=box_shape[2], n_w=n_w), **kw)
+        self.plan = ops.tile_tables(box, g, long_shape=tuple(img.shape[2:]), box_shape=box_shape, device=img.device)
+        rows = nb * img.shape[0] * int(np.prod(img.shape[2:]))
+        self.e_long = torch.empty((rows, model.model.diffusion_model.out_channels), dtype=torch.float32, device=img.device)
+
+    def _evaluate(self):
+        return self.model.apply_model_tiles(self.img, self.prep, self.t_table, self.plan, self.e_long,
+                                            t_index=self.counter)
+
+
+_tiled_classes = {}
+
+
+def tiled(run_class):
+    """The tiled form of a FusedRun class (FusedRun itself, DpmRun): TiledRun mixed in ahead of it."""
+    if run_class not in _tiled_classes:
+        _tiled_classes[run_class] = type("Tiled" + run_class.__name__, (TiledRun, run_class), {})
+    return _tiled_classes[run_class]
+
+
+class _TiledModel:
+    """The generic path's tiles, in the manner of _WindowedModel: a stand-in for the model whose apply_model evaluates
+    the wrapped model on every box of the current step (`step`, set by the sampling loop) that carries weight and blends
+    the outputs with the same plan tables, in plain torch indexing on the device. Every other attribute is the wrapped
+    model's."""
+
+    def __init__(self, model, box, g, box_shape, device):
+        self._m, self._box, self._g, self._shape, self._dev = model, box, g, tuple(box_shape), device
+        self.step = 0
+
+    def __getattr__(self, name):
+        return getattr(self._m, name)
+
+    def apply_model(self, x, t, c, **kw):
+        (T, h, w), out = self._shape, None
+        for k, (t0, y0, x0) in enumerate(self._box[self.step].tolist()):
+            wt = box_weights(self._g[self.step, k], self._shape)     # dc_tile_merge's two fp32 product roundings
+            if not wt.any():
+                continue                                # padding box
+            crop = lambda v: v[:, :, t0:t0 + T, y0:y0 + h, x0:x0 + w].contiguous()
+            cw = c
+            if isinstance(c, dict) and c.get("c_concat") is not None:
+                cw = dict(c, c_concat=[crop(cc) for cc in c["c_concat"]])
+            e = self._m.apply_model(crop(x), t, cw, **kw).to(torch.float32)
+            if out is None:
+                out = torch.zeros(x.shape[:1] + e.shape[1:2] + x.shape[2:], dtype=torch.float32, device=x.device)
+            # dc_tile_merge's order and roundings, in ascending box index, through float64 as _WindowedModel does (a fused
+            # multiply-add except for rare double roundings)
+            seg = out[:, :, t0:t0 + T, y0:y0 + h, x0:x0 + w]
+            seg.copy_((seg.double() + torch.from_numpy(wt).to(self._dev).double().view(1, 1, T, h, w) * e.double()).float())
+        return out
+
+
 class DDIMSampler(object):
     def __init__(self, model, schedule="linear", **kwargs):
         super().__init__()
@@ -496,7 +588,7 @@ class DDIMSampler(object):
                       noise_dropout=0., score_corrector=None, corrector_kwargs=None, unconditional_guidance_scale=1.,
                       unconditional_conditioning=None, verbose=True, precision=None, fs=None, guidance_rescale=0.0,
                       noises=None, use_graph=False, window_stride=None, window_weights="triangle", window_shift=0,
-                      windows_per_call=None, apg=None, **kwargs):
+                      windows_per_call=None, apg=None, tiles=None, **kwargs):
         if ddim_use_original_steps or quantize_denoised or score_corrector is not None or noise_dropout > 0.:
             raise NotImplementedError("only the options DynamiCrafter inference uses are implemented "
                                       "(no original-steps / quantised / corrected sampling)")
@@ -507,7 +599,8 @@ class DDIMSampler(object):
                              unconditional_conditioning=unconditional_conditioning, fs=fs,
                              guidance_rescale=guidance_rescale, noises=noises, use_graph=use_graph,
                              window_stride=window_stride, window_weights=window_weights, window_shift=window_shift,
-                             windows_per_call=windows_per_call, apg=apg, **kwargs)
+                             windows_per_call=windows_per_call, apg=apg, **({} if tiles is None else {"tiles": tiles}),
+                             **kwargs)
 
     def subset_steps(self, timesteps):
         """How many steps `ddim_sampling(timesteps=k)` runs: the DDIM indices range(S)[:subset_end], descending, with the
@@ -521,7 +614,7 @@ class DDIMSampler(object):
     def _denoise(self, n, cond, shape, x_T=None, callback=None, mask=None, x0=None, img_callback=None, log_every_t=100,
                  temperature=1., unconditional_guidance_scale=1., unconditional_conditioning=None, fs=None,
                  guidance_rescale=0.0, noises=None, use_graph=False, window_stride=None, window_weights="triangle",
-                 window_shift=0, windows_per_call=None, apg=None, **kwargs):
+                 window_shift=0, windows_per_call=None, apg=None, tiles=None, **kwargs):
         """The last `n` steps of the schedule from x_T (all S of them: ddim_sampling; fewer: timesteps= and decode).
         Executed step i of the n is step S - n + i of the full run and indexes `noises` / `q_noises` ([n, ...]) by i."""
         m = self.model
@@ -538,9 +631,29 @@ class DDIMSampler(object):
             return img, {"x_inter": [img.clone()], "pred_x0": [img.clone()]}
         if n < S_all and window_stride is not None:
             raise ValueError("window_stride cannot be combined with a partial run (timesteps= / decode)")
+        if n < S_all and tiles is not None:
+            raise ValueError("tiles cannot be combined with a partial run (timesteps= / decode)")
         S, off = n, S_all - n
-        window = None
-        if window_stride is not None:
+        window = tile = None
+        if tiles is not None:
+            # spatial tiles; `window_stride` beside them tiles the time axis of the same product plan
+            options.check_keys(options.EXTENT_OPTIONS["tiles"], tiles)
+            cfg = tiles_config(tiles, options.EXTENT_OPTIONS["tiles"].keys)
+            net = getattr(getattr(m, "model", None), "diffusion_model", None)
+            if hasattr(net, "spatial_multiple"):
+                check_box(cfg["size"], net.spatial_multiple())
+            T = getattr(m, "temporal_length", None) if window_stride is not None else img.shape[2]
+            if T is None:
+                raise ValueError("windowed sampling needs the model's temporal_length (the frames one UNet call takes)")
+            box_shape = (int(T),) + cfg["size"]
+            stride = (1 if window_stride is None else window_stride,) + cfg["stride"]
+            shift = (0 if window_stride is None else window_shift,) + cfg["shift"]
+            weights = cfg["weights"]                    # one name for every axis
+            plan_host = tile_plan(tuple(img.shape[2:]), box_shape, stride, weights, shift, S)
+            per_call = cfg["per_call"] if cfg["per_call"] is not None else windows_per_call
+            tile = dict(T=box_shape[0], h=box_shape[1], w=box_shape[2], stride=stride, weights=weights, shift=shift,
+                        per_call=per_call, plan=plan_host)
+        elif window_stride is not None:
             T = getattr(m, "temporal_length", None)
             if T is None:
                 raise ValueError("windowed sampling needs the model's temporal_length (the frames one UNet call takes)")
@@ -577,6 +690,8 @@ class DDIMSampler(object):
         run = None
         if self._fused(branches):
             cls, wkw = (self._run_class, {}) if window is None else (windowed(self._run_class), dict(window=window))
+            if tile is not None:
+                cls, wkw = tiled(self._run_class), dict(tile=tile)
             run = cls(self, img, branches, fs=fs, noises=noises, cfg_scale=unconditional_guidance_scale,
                       cfg_img=kwargs.get("cfg_img"), guidance_rescale=guidance_rescale, temperature=temperature,
                       mask=mask, x0=x0, q_noises=q_noises, clean_cond=clean_cond, **wkw,
@@ -585,12 +700,15 @@ class DDIMSampler(object):
                 run.capture()
         else:
             noises, blend = _step_inputs(img, S, noises, mask, x0, q_noises, clean_cond,
-                                         long_branches=None if window is None else branches)
+                                         long_branches=None if window is None and tile is None else branches,
+                                         long_space=tile is not None)
         proxy = None
         if run is None:
             if window is not None:
                 # the update's apply_model calls go to a stand-in that evaluates the model per window and blends
                 proxy = _WindowedModel(m, *plan_host, window["T"], dev)
+            if tile is not None:
+                proxy = _TiledModel(m, *plan_host, (tile["T"], tile["h"], tile["w"]), dev)
             update = self._generic_update(img, branches, dict(g, unconditional_conditioning=unconditional_conditioning),
                                           kwargs, **({} if proxy is None else {"model": proxy}))
         for i in range(S):
@@ -683,7 +801,7 @@ class DDIMSampler(object):
         keywords of samplers/options.py (`freeu=`, `apg=`, `token_downsampling=`) and no other."""
         if use_original_steps:
             raise NotImplementedError
-        unexpected = sorted(set(sampling_options) - set(OPTIONS))
+        unexpected = sorted(set(sampling_options) - set(OPTIONS) - set(options.EXTENT_OPTIONS))
         if unexpected:
             raise TypeError(f"decode() got an unexpected keyword argument {unexpected[0]!r}")
         n = len(self.ddim_timesteps[:t_start])
@@ -721,6 +839,8 @@ class DDIMSampler(object):
                                  f"is not defined")
         if kwargs.get("window_stride") is not None:
             raise ValueError("encode: windowed (long-clip) inversion is not defined")
+        if kwargs.get("tiles") is not None:
+            raise ValueError("encode: tiled (large-frame) inversion is not defined")
         S = self.ddim_timesteps.shape[0]
         if not isinstance(t_enc, (int, np.integer)) or not 1 <= t_enc <= S:
             raise ValueError(f"encode: t_enc must be an integer in 1 .. {S}, got {t_enc!r}")

@@ -7,6 +7,11 @@ An option is one of two kinds:
                  `takes_model_settings`). The UNet validates it: `set_<name>(cfg)` enables cfg (None: disables) and returns
                  the setting that was in force.
   RUN_SETTING    handed to the run, which owns whatever state it needs (`apg=`: validated by ddim.apg_config / check_apg).
+
+OPTIONS holds the options that act on a latent of the model's own extent. EXTENT_OPTIONS holds the run settings that
+change what extent a call denoises (`tiles=`: frames larger than the trained size, samplers/tiles.py); they
+are a table of their own because they are no guidance - an inversion or a partial run refuses them for its own reason,
+as it refuses `window_stride` - and the same helpers (`fold`, `documented`, the parser helpers) serve both tables.
 """
 import argparse
 import contextlib
@@ -66,6 +71,36 @@ OPTIONS = {o.name: o for o in (
 )}
 
 
+def _tiles_from_flags(tile=None, **secondary):
+    """The command line gives pixels; `tiles.tiles_from_pixels` converts with the autoencoder's factor."""
+    if tile is None:
+        raise ValueError(f"--{next(iter(secondary))} needs --tile HEIGHT WIDTH")
+    stride = secondary.get("tile_stride")
+    return dict(size=tuple(tile), stride=None if stride is None else tuple(stride),
+                shift=tuple(secondary.get("tile_shift", (0, 0))))
+
+
+EXTENT_OPTIONS = {o.name: o for o in (
+    Option("tiles", "spatial tiles", RUN_SETTING, dict(size=REQUIRED, stride=None, weights="triangle", shift=(0, 0), per_call=None),
+           "`tiles` (not in the reference): None, or dict(size=(h, w), stride=None, weights=\"triangle\", shift=(0, 0), "
+           "per_call=None) in latent units - spatially tiled sampling of a latent larger than `size`, the size the model was "
+           "trained at: the UNet denoises overlapping boxes of `size` (stride: default size // 2 per axis) and their outputs "
+           "are blended ahead of the unchanged update (lvdm/models/samplers/tiles.py, DESIGN 4.16). Full runs only; beside "
+           "`window_stride` the time axis is tiled as well.",
+           (("--tile", dict(type=int, nargs=2, metavar=("HEIGHT", "WIDTH"), help="spatially tiled sampling: the tile size in "
+                            "pixels (the size the model was trained at) for --height / --width larger than it; default off")),
+            ("--tile_stride", dict(type=int, nargs=2, metavar=("SY", "SX"), help="tile stride in pixels (default half a tile)")),
+            ("--tile_shift", dict(type=int, nargs=2, metavar=("DY", "DX"), help="pixels the interior tile seams move per step "
+                                  "(default 0 0)"))),
+           _tiles_from_flags),
+)}
+
+
+def all_options():
+    """Every option of both tables, OPTIONS first."""
+    return {**OPTIONS, **EXTENT_OPTIONS}
+
+
 def of_kind(kind):
     return [o for o in OPTIONS.values() if o.kind == kind]
 
@@ -123,7 +158,7 @@ def documented(fn):
     """Appends every option's paragraph to the docstring of a function that takes them."""
     last = fn.__doc__.rstrip().split("\n")[-1]
     indent = last[:len(last) - len(last.lstrip())]          # a one-line docstring: none
-    fn.__doc__ = "\n".join([fn.__doc__.rstrip()] + [indent + o.doc for o in OPTIONS.values()])
+    fn.__doc__ = "\n".join([fn.__doc__.rstrip()] + [indent + o.doc for o in all_options().values()])
     return fn
 
 
@@ -131,19 +166,19 @@ def documented(fn):
 def add_option_arguments(parser):
     """Every option's flags. They appear in the namespace only when given (`from_args` reads them): without them a run's
     arguments are what they were."""
-    for opt in OPTIONS.values():
+    for opt in all_options().values():
         for flag, kw in opt.flags:
             parser.add_argument(flag, default=argparse.SUPPRESS, **kw)
 
 
 def from_args(name, args):
     """The flags of option `name` in a parsed namespace as its dict, or None."""
-    opt = OPTIONS[name]
+    opt = all_options()[name]
     given = {d: getattr(args, d) for d in (flag.lstrip("-") for flag, _ in opt.flags) if getattr(args, d, None) is not None}
     return opt.from_flags(**given) if given else None
 
 
 def options_from_args(args):
     """{name: dict} of the options a parsed namespace gives."""
-    out = {name: from_args(name, args) for name in OPTIONS}
+    out = {name: from_args(name, args) for name in all_options()}
     return {k: v for k, v in out.items() if v is not None}

@@ -881,6 +881,11 @@ class UNetModel(nn.Module):
                     ds //= 2
         return best
 
+    def spatial_multiple(self):
+        """What the latent's height and width must divide by: a factor 2 per downsampling level, or the decoder's
+        upsampled rows do not meet the skips (forward_rows: 'skip / decoder resolution mismatch')."""
+        return 2 ** sum(1 for blk in self._layout[0] for kind, _ in blk if kind == "down")
+
     def max_context_row_width(self):
         """The widest buffer with one row per context token: the context itself, or the 4 ch wide k / v / k_ip / v_ip
         projection of the widest SpatialTransformer (_context_kv)."""

@@ -749,6 +749,62 @@ def window_merge(e, out, plan, *, nb, B, C, HW, w0=0, n_w=None, index=0, step_in
     return out
 
 
+def tile_tables(box, g, *, long_shape, box_shape, device):
+    """The device tables of a tile plan (samplers/tiles.py): box int32 [S, W, 3], g fp32 [S, W, T + h + w]. The C entries
+    cannot look into device memory, so the values are checked here, on the host copy, before upload (check_tiles): every
+    start in range, weights finite, >= 0 and summing to 1 on every position of every step."""
+    import numpy as np
+    from .lvdm.models.samplers.tiles import check_tiles
+    box = np.ascontiguousarray(box, dtype=np.int32)
+    g = np.ascontiguousarray(g, dtype=np.float32)
+    long_shape, box_shape = tuple(int(v) for v in long_shape), tuple(int(v) for v in box_shape)
+    S, W = check_tiles(box, g, long_shape, box_shape)
+    return dict(box=torch.from_numpy(box).to(device), g=torch.from_numpy(g).to(device), S=S, W=W, long_shape=long_shape,
+                box_shape=box_shape, host_box=box, host_g=g)
+
+
+def _need_tiles(plan, w0, n_w, index, step_index):
+    S, W = plan["S"], plan["W"]
+    if w0 < 0 or n_w < 1 or w0 + n_w > W:
+        raise ValueError(f"boxes {w0} .. {w0 + n_w - 1} are not all in the plan's {W}")
+    if step_index is None and not 0 <= index < S:
+        raise ValueError(f"step {index} is outside the plan's {S} steps")
+    for t, dt, n, nm in ((plan["box"], torch.int32, S * W * 3, "box"),
+                         (plan["g"], torch.float32, S * W * sum(plan["box_shape"]), "g")):
+        if t.dtype != dt or not t.is_contiguous() or not t.is_cuda:
+            raise ValueError(f"tile plan: {nm} must be a contiguous CUDA {dt} tensor")
+        _need(t, n, nm)
+    return S, W
+
+
+def pack_latent_tiles(x, cc, out, plan, *, B, Cx, Cc, w0=0, n_w=None, index=0, step_index=None, nrep=1):
+    """pack_latent for the boxes w0 .. w0 + n_w - 1 of the current step of `plan` (tile_tables): rows
+    [(rep, b, w, f, y, x)][c_pad] (dc_pack_latent_tiles). x, cc: fp32 [B, C, T_long, H_long, W_long]."""
+    n_w = plan["W"] - w0 if n_w is None else n_w
+    S, W = _need_tiles(plan, w0, n_w, index, step_index)
+    (TL, HL, WL), (T, H, Wd) = plan["long_shape"], plan["box_shape"]
+    _need(x, B * Cx * TL * HL * WL, "x"); _need(cc, B * Cc * TL * HL * WL, "c_concat")
+    _rows(out, "out"); _need_rows(out, nrep * B * n_w * T * H * Wd, Cx + Cc, "out")
+    check(_hip.lib().dc_pack_latent_tiles(_ptr(x), _ptr(cc), _ptr(out), _ptr(plan["box"]), _ptr(step_index), index, S, W,
+                                          w0, n_w, B, Cx, Cc, TL, HL, WL, T, H, Wd, out.stride(0), nrep, stream_ptr()),
+          "dc_pack_latent_tiles")
+    return out
+
+
+def tile_merge(e, out, plan, *, nb, B, C, w0=0, n_w=None, index=0, step_index=None, accumulate=False):
+    """out rows [(k, b, F, Y, X)][ld_out] = the weighted blend of the box rows e [(k, b, w, f, y, x)][ld_e] of the boxes
+    w0 .. w0 + n_w - 1 (dc_tile_merge); accumulate adds to `out` (chunked evaluation, ascending chunks)."""
+    n_w = plan["W"] - w0 if n_w is None else n_w
+    S, W = _need_tiles(plan, w0, n_w, index, step_index)
+    (TL, HL, WL), (T, H, Wd) = plan["long_shape"], plan["box_shape"]
+    _rows(e, "e", torch.float32); _rows(out, "out", torch.float32)
+    _need_rows(e, nb * B * n_w * T * H * Wd, C, "e"); _need_rows(out, nb * B * TL * HL * WL, C, "out")
+    check(_hip.lib().dc_tile_merge(_ptr(e), e.stride(0), _ptr(out), out.stride(0), _ptr(plan["box"]), _ptr(plan["g"]),
+                                   _ptr(step_index), index, S, W, w0, n_w, nb, B, C, TL, HL, WL, T, H, Wd,
+                                   1 if accumulate else 0, stream_ptr()), "dc_tile_merge")
+    return out
+
+
 def nchw_to_rows(x, out, *, N, Cc, HW, scale=1.0):
     _need(x, N * Cc * HW, "x"); _need_rows(out, N * HW, Cc, "out")
     check(_hip.lib().dc_nchw_to_rows(_ptr(x), _ptr(out), N, Cc, HW, out.stride(0), scale, stream_ptr()),

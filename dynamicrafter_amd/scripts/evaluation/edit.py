@@ -41,7 +41,7 @@ def video_guided_synthesis(model, prompts, videos, source, noise_shape, n_sample
                            unconditional_guidance_scale=1.0, cfg_img=None, fs=None, text_input=False,
                            multiple_cond_cfg=False, timestep_spacing="uniform", guidance_rescale=0.0, strength=0.6,
                            invert=True, source_prompts=None, freeu=None, apg=None, token_downsampling=None,
-                           **kwargs):
+                           tiles=None, **kwargs):
     """Returns [batch, n_samples, c, t, h, w] decoded frames. `videos` [b, 3, t, h, w] is what `load_data_prompts` gives for
     the EDITED first frame (that frame over all frames), `source` [b, 3, t, h, w] what `load_video_batch` gives for the
     clip to edit; the other arguments are `image_guided_synthesis`'s. n = strength_steps(strength, ddim_steps) steps run.
@@ -58,8 +58,11 @@ def video_guided_synthesis(model, prompts, videos, source, noise_shape, n_sample
     ValueError: their conditioning or solver has no defined inverse here.
     The model settings among the options below are in force for the inversion and the denoise alike, so that the denoise
     runs the model the inversion inverted; `apg` goes to the denoise (`DDIMSampler.decode`): the inversion runs at guidance
-    scale 1 and has none."""
-    options.fold(kwargs, freeu=freeu, apg=apg, token_downsampling=token_downsampling)
+    scale 1 and has none. `tiles` goes to the denoise too, which takes it for a full run only (strength 1 without an
+    inversion): a tiled inversion is not defined, and a partial run refuses tiles."""
+    if tiles is not None and invert:
+        raise ValueError("video_guided_synthesis: tiles with invert=True is not supported (a tiled inversion is not defined)")
+    options.fold(kwargs, freeu=freeu, apg=apg, token_downsampling=token_downsampling, tiles=tiles)
     with options.model_settings_scope(model, kwargs):
         return _video_guided_synthesis(model, prompts, videos, source, noise_shape, n_samples, ddim_steps, ddim_eta,
                                        unconditional_guidance_scale, cfg_img, fs, text_input, multiple_cond_cfg,

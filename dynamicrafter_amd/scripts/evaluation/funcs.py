@@ -27,7 +27,7 @@ from .inference import get_latent_z, load_model_checkpoint, load_prompts  # noqa
 @torch.no_grad()
 @options.documented
 def batch_ddim_sampling(model, cond, noise_shape, n_samples=1, ddim_steps=50, ddim_eta=1.0, cfg_scale=1.0,
-                        temporal_cfg_scale=None, freeu=None, apg=None, token_downsampling=None, **kwargs):
+                        temporal_cfg_scale=None, freeu=None, apg=None, token_downsampling=None, tiles=None, **kwargs):
     """funcs.py:14-80. `cond` is {"c_crossattn": [...], "c_concat": [...], "fs": tensor}; "fs" is taken out of it (the caller's
     dict comes back without it, as in the reference). A latent width of 32 (the 256 model) samples with "uniform" spacing and no
     guidance rescale, any other width with "uniform_trailing" and 0.7. With cfg_scale != 1 the unconditional branch is a copy of
@@ -39,7 +39,7 @@ def batch_ddim_sampling(model, cond, noise_shape, n_samples=1, ddim_steps=50, dd
     argument reaches `DDIMSampler.sample` (`x_T`, `noises`, `use_graph`, `window_stride`, ...), except `sampler=`, which picks
     the sampler class as in `image_guided_synthesis` ("ddim", "dpmpp_2m", "dpmpp_2m_sde").
     Here `apg` takes the place of the guidance rescale of 0.7, which is then not applied."""
-    options.fold(kwargs, freeu=freeu, apg=apg, token_downsampling=token_downsampling)
+    options.fold(kwargs, freeu=freeu, apg=apg, token_downsampling=token_downsampling, tiles=tiles)
     ddim_sampler = make_sampler(model, kwargs.pop("sampler", "ddim"))
     kwargs.pop("temporal_length", None)
     kwargs.pop("conditional_guidance_scale_temporal", None)

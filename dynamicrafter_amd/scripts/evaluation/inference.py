@@ -115,6 +115,29 @@ def build_conditioning(model, prompts, videos, unconditional_guidance_scale=1.0,
     return cond, uc, uc_2
 
 
+def check_ae_extent(model, noise_shape):
+    """The autoencoder runs on whole frames of a tiled call, whatever their size. Its scratch buffers are limited to 2^31
+    elements (ops.Arena refuses a larger one with a ValueError of its own, but only in the middle of the encode or the
+    decode): the two that grow fastest are checked here, ahead of the sampling, and the limit is named. They are the
+    score matrix of the mid-block attention, (h w)^2 for a latent frame of h x w, and the full-resolution activations of
+    one call, frames x pixels x channels."""
+    dd = getattr(getattr(model, "first_stage_model", None), "ddconfig", None)
+    if dd is None:
+        return
+    h, w = int(noise_shape[3]), int(noise_shape[4])
+    if (h * w) ** 2 >= 2 ** 31:
+        raise ValueError(f"tiles: a latent frame of {h} x {w} = {h * w} positions exceeds what the autoencoder's mid-block "
+                         f"attention takes (its score matrix of (h w)^2 elements must stay under 2^31: h w <= 46340)")
+    mult = list(dd["ch_mult"])
+    f = 2 ** (len(mult) - 1)
+    frames = max(1, getattr(model, "ae_frames_per_call", 1)) if getattr(model, "perframe_ae", False) \
+        else int(noise_shape[0]) * int(noise_shape[2])
+    width = dd["ch"] * max(mult[:2])                     # the widest buffer at full resolution (a level-0 ResBlock's input)
+    if frames * h * f * w * f * width >= 2 ** 31:
+        raise ValueError(f"tiles: {frames} frames of {h * f} x {w * f} pixels per autoencoder call exceed its 2^31-element "
+                         f"buffer limit at {width} channels (decode frame by frame: perframe_ae)")
+
+
 @torch.no_grad()
 @options.documented
 def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddim_steps=50, ddim_eta=1.,
@@ -122,7 +145,7 @@ def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddi
                            multiple_cond_cfg=False, loop=False, interp=False, timestep_spacing="uniform",
                            guidance_rescale=0.0, use_fixed_scheduler=False, sampler="ddim", num_frames=None,
                            window_stride=None, window_weights="triangle", window_shift=0, freeu=None, apg=None,
-                           token_downsampling=None, **kwargs):
+                           token_downsampling=None, tiles=None, **kwargs):
     """inference.py:216-313. Returns [batch, n_samples, c, t, h, w] decoded frames.
 
     `use_fixed_scheduler` is accepted and ignored: the fork's "fixed" sampler only patches sigma so that
@@ -138,8 +161,16 @@ def image_guided_synthesis(model, prompts, videos, noise_shape, n_samples=1, ddi
     temporal_length // 2): the image latent is repeated over `num_frames` for c_concat, `x_T` / `noises` passed through
     are `num_frames` long, and all frames are decoded. `window_stride` alone asks for windows at the clip's own length.
     Not with `loop` / `interp`: their c_concat is zero on interior frames, so interior windows would see a conditioning
-    the model never met."""
-    options.fold(kwargs, freeu=freeu, apg=apg, token_downsampling=token_downsampling)
+    the model never met.
+    With `tiles`, `noise_shape` and `videos` are at the large size: the large image is encoded for c_concat and the large
+    latent decoded by the same autoencoder, frame by frame. `loop` / `interp` work with spatial tiles, since every tile
+    holds the first and the last frame; they stay refused when the time axis is tiled too."""
+    options.fold(kwargs, freeu=freeu, apg=apg, token_downsampling=token_downsampling, tiles=tiles)
+    if tiles is not None:
+        if window_stride is not None and (loop or interp):
+            raise ValueError(f"tiles with window_stride = {window_stride} cannot be combined with loop = {loop} / interp = "
+                             f"{interp}: boxes inside the clip would be conditioned on all-zero c_concat frames")
+        check_ae_extent(model, noise_shape)
     T_model = getattr(model, "temporal_length", None)
     if num_frames is not None:
         if loop or interp:
@@ -404,6 +435,9 @@ def run_inference(args, gpu_num, gpu_no, device=None):
 
     extra = {k: getattr(args, k) for k in ("sampler", "num_frames", "window_stride") if getattr(args, k, None) is not None}
     extra.update(options.options_from_args(args))
+    if "tiles" in extra:                                  # --tile gives pixels; the keyword takes latent units
+        from ...lvdm.models.samplers.tiles import tiles_from_pixels
+        extra["tiles"] = tiles_from_pixels(extra["tiles"], args.height // h)
     save_kw = dict(container=getattr(args, "container", "apng"), quality=getattr(args, "quality", 90))
     written = []
     start = time.time()

@@ -185,12 +185,12 @@ class DynamiCrafterImg2VideoPipeline:
     def __call__(self, image, prompt="", negative_prompt=None, num_inference_steps=50, guidance_scale=7.5, eta=0.0,
                  frame_stride=3, num_frames=None, height=None, width=None, num_videos_per_prompt=1, generator=None,
                  latents=None, output_type="tensor", return_dict=True, callback=None, callback_steps=1,
-                 cross_attention_kwargs=None, freeu=None, apg=None, token_downsampling=None, **kwargs):
+                 cross_attention_kwargs=None, freeu=None, apg=None, token_downsampling=None, tiles=None, **kwargs):
         """:398-530. Returns {"videos": v} (or v with return_dict=False); v is [b, 3, num_frames, height, width] as a device
         tensor ("tensor"), an ndarray ("numpy") or b lists of PIL frames ("pil"). Extra **kwargs reach DDIMSampler.sample.
         `freeu` and `token_downsampling` below hold for this call only; enable_freeu / enable_token_downsampling set them for
         every later call."""
-        options.fold(kwargs, freeu=freeu, apg=apg, token_downsampling=token_downsampling)
+        options.fold(kwargs, freeu=freeu, apg=apg, token_downsampling=token_downsampling, tiles=tiles)
         if isinstance(prompt, str):
             prompt = [prompt]
         batch_size = len(prompt)

@@ -198,6 +198,36 @@ int dc_window_merge(const float* e, int ld_e, float* out, int ld_out, const int3
                     const int32_t* step_index, int index, int S, int W, int w0, int n_w, int nb, int B, int C, int T_long,
                     int T, int HW, int accumulate, void* stream);
 
+/* dc_pack_latent for boxes of the UNet's own extent (T, H, Wd) inside a latent of (T_long, H_long, W_long) (spatially tiled
+ * sampling: frames larger than the trained size; the time axis may be tiled as well). x [B,Cx,T_long,H_long,W_long],
+ * cc [B,Cc,T_long,H_long,W_long] fp32 -> channels-last bf16 rows [(rep, b, w, f, y, x)][c_pad] for the boxes
+ * w = w0 .. w0+n_w-1 of one step: position (f, y, x) of box w is long position (t0 + f, y0 + y, x0 + x) with
+ * (t0, y0, x0) = box[(step*W + w)*3 ..], channels >= Cx+Cc zeroed; (b, w) is the clip index of the UNet batch. box: int32
+ * [S][W][3] device table, every start in [0, long - extent] of its axis (one outside is clamped into it);
+ * step = step_index[0] (device counter) or `index`; a counter outside [0, S) launches nothing. The per-element conversion is
+ * dc_pack_latent's: every row is bit-identical to dc_pack_latent on the cropped tensors.
+ * no reference call site (the reference samples one latent size per config): MultiDiffusion, Bar-Tal et al.,
+ * arXiv:2302.08113 */
+int dc_pack_latent_tiles(const float* x, const float* cc, uint16_t* out, const int32_t* box, const int32_t* step_index,
+                         int index, int S, int W, int w0, int n_w, int B, int Cx, int Cc, int T_long, int H_long,
+                         int W_long, int T, int H, int Wd, int c_pad, int nrep, void* stream);
+
+/* Blend of the UNet's box outputs onto the long latent. e: fp32 rows [(k, b, w, f, y, x)][ld_e] (nb branches k, n_w boxes,
+ * first C channels valid) -> out: fp32 rows [(k, b, F, Y, X)][ld_out], which dc_ddim_step / dc_dpmpp_step read as branch k at
+ * row offset k*B*T_long*H_long*W_long:
+ *   out[k,b,F,Y,X,c] = sum_w fl(fl(gt_w[F - t0_w] * gy_w[Y - y0_w]) * gx_w[X - x0_w]) * e[k,b,w,F - t0_w,Y - y0_w,X - x0_w,c]
+ * over the boxes w0 <= w < w0+n_w that contain (F, Y, X), in ascending w (first term a product, then fused multiply-adds);
+ * fl is rounding to fp32 and (gt_w | gy_w | gx_w) = g[(step*W + w)*(T+H+Wd) ..], the box's three per-axis weight vectors.
+ * A term of weight 0 (padding box) is skipped and its e never read. Any two runs agree bitwise and a single box of weight 1
+ * returns its input, the sign of zero included. accumulate == 0 writes (0 where no box of the call covers the position),
+ * != 0 adds to what out holds: boxes evaluated in chunks of n_w give the unchunked values (equal as numbers; a position whose
+ * first term comes in a later chunk receives it through a multiply-add onto +0, so a -0 product becomes +0). g: fp32
+ * [S][W][T+H+Wd] device table, each axis normalised so that the product weights of the boxes containing a position sum to 1.
+ * no reference call site: arXiv:2302.08113 (eq. 5, the closed-form blend) */
+int dc_tile_merge(const float* e, int ld_e, float* out, int ld_out, const int32_t* box, const float* g,
+                  const int32_t* step_index, int index, int S, int W, int w0, int n_w, int nb, int B, int C, int T_long,
+                  int H_long, int W_long, int T, int H, int Wd, int accumulate, void* stream);
+
 /* Generic layout helpers (channels-last bf16 <-> NCHW fp32), used at the AutoencoderKL boundary.
  * nchw_to_rows: x[N][C][HW] fp32 -> rows[N*HW][c_pad] bf16 (scaled by `scale`, pad channels zero)
  * rows_to_nchw: rows[N*HW][ld] (bf16 or f32) -> y[N][C][HW] fp32 */
